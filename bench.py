@@ -6,12 +6,17 @@ the product path: forward, NLL, backward, DP all-reduce, fused clip + Adam, lagg
 check) on a 3-tier SampleRNN, dim 1024, frame_sizes [16, 4], 6 speakers + 43-d Ahocoder
 conditioning, T = 1024, bf16 MFMA with fp32 master weights / recurrences.  On one GPU the
 Trainer runs in graph mode: the warm-up chunks run the eager steps and capture the step, the
-timed chunks replay it (`graph_replays`; `eager_ms_per_step` = the same step enqueued kernel
-by kernel, measured right after).
+timed chunks replay it (`graph_replays`; with --full, `eager_ms_per_step` = the same step
+enqueued kernel by kernel, measured right after).
 
 Default workload = configs[3]: global batch 512 stream rows sharded over the N ranks
-(512 / N rows per GPU, strong scaling; N = 1 is the whole 512-row batch on one GPU).  Beside
-it the line carries
+(512 / N rows per GPU, strong scaling; N = 1 is the whole 512-row batch on one GPU).
+
+A plain run does only what that headline needs: set-up, the warm-up chunks, the --steps timed
+chunks, the outputs of --dump-outputs, the result line (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` = milliseconds per timed step, and the headline's
+own fields; the fields of the measurements below are null / empty).  With --full the line
+also carries
   * `config_b` (N = 1): configs[1], 128 rows on one GPU;
   * `handwritten_only` (N = 1, bf16): the headline step with every GEMM on the hand-written
     kernels (SRNN_BLASLT=0);
@@ -29,7 +34,15 @@ it the line carries
   * `cpu_baseline`: the oracle (torch-CPU restatement) on the host cores, bounded samples of
     the TBPTT step at configs[1]'s batch and of generation at configs[2]'s.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch ROWS_PER_GPU] [--no-gen]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch ROWS_PER_GPU]
+                  [--dump-outputs DIR] [--full [--no-gen] [--no-cpu] [--no-extra]]
+
+--dump-outputs DIR writes what the timed path handed back in its last timed step (rank 0's
+rows) as DIR/<name>.npy, float32: `loss` and `log_probs` (what the Trainer gives its
+iteration plugins), `hidden.<tier>` (the carried hidden state) and `param.<name>` (every
+parameter after the step's update).  Arrays too large for the 48 MB budget of a dump are
+stored as a fixed, seeded sample of their flattened entries (dump_sample_index).  Weights and
+synthetic chunks are seeded, so the same arguments give the same inputs in every run.
 
 --gpus N > 1 outside torchrun spawns the N ranks itself (spawn_ranks: N child processes with
 the torchrun environment, the parent touching no GPU); under torchrun (WORLD_SIZE set) each
@@ -72,23 +85,36 @@ def make_model(dtype, seed=77977, frame_sizes=(16, 4), cond_dim=43):
     return m, pred
 
 
-def synth_batches(B, T, L, n_chunks, row0, seed=0):
+def synth_batches(B, T, L, n_chunks, row0, seed=0, dev=None):
     """Stateful TBPTT layout (dataset.py:155-163, 242-289) on synthetic 16 kHz streams:
-    sum of 3 sinusoids + Laplacian noise, float64 mu-law quantised, cond U[0,1), spk b%6."""
+    sum of 3 sinusoids + Laplacian noise, float64 mu-law quantised, cond U[0,1), spk b%6.
+    The rows are independent and are synthesised and quantised on a pool of host threads.
+    With `dev` the streams go to that device whole and the chunks are cut there (the same
+    tensors as gpu_batches of the host chunks)."""
+    from concurrent.futures import ThreadPoolExecutor
     import recipe
+    import samplernn_hip as H
     import utils
     total = n_chunks * T + L
-    audio = np.stack([recipe.synth_audio(total, seed + row0 + b) for b in range(B)])
-    idx = utils.uquantize(torch.from_numpy(audio), 256)           # host, float64 path
+    idx = torch.empty(B, total, dtype=torch.long)
+    H.lib()                                 # (loaded before the threads call into it)
+
+    def row(b):
+        audio = recipe.synth_audio(total, seed + row0 + b)
+        idx[b] = utils.uquantize(torch.from_numpy(audio), 256)    # host, float64 path
+    with ThreadPoolExecutor(min(16, host_cores()['usable'])) as pool:
+        list(pool.map(row, range(B)))
     rng = np.random.Generator(np.random.PCG64(seed + 1000 + row0))
-    cond = rng.uniform(0, 1, (B, n_chunks * T // L, 43))
-    spk = ((np.arange(B) + row0) % 6).reshape(B, 1)
+    cond = torch.from_numpy(rng.uniform(0, 1, (B, n_chunks * T // L, 43)))
+    spk = torch.from_numpy(((np.arange(B) + row0) % 6).reshape(B, 1))
+    if dev is not None:
+        idx, cond, spk = idx.to(dev), cond.to(dev), spk.to(dev)
     out = []
     for n in range(n_chunks):
         inp = idx[:, n * T: n * T + L + T - 1].contiguous()
         tgt = idx[:, n * T + L: n * T + L + T].contiguous()
-        cnd = torch.from_numpy(np.ascontiguousarray(cond[:, n * T // L:(n + 1) * T // L]))
-        out.append((inp, n == 0, tgt, cnd, torch.from_numpy(spk)))
+        cnd = cond[:, n * T // L:(n + 1) * T // L].contiguous()
+        out.append((inp, n == 0, tgt, cnd, spk))
     return out
 
 
@@ -161,26 +187,76 @@ SITE_NOTES = {
 
 class _LossLog:
     """Trainer 'iteration' plugin keeping a copy of every step's loss (a replayed graph step
-    hands out the same static loss buffer each time)."""
+    hands out the same static loss buffer each time) and, when `keep_output`, a reference to
+    the last step's output."""
 
-    def __init__(self):
+    def __init__(self, keep_output=False):
         self.trigger_interval = [(1, 'iteration')]
         self.values = []
+        self.keep_output = keep_output
+        self.output = None
 
     def register(self, trainer):
         pass
 
     def iteration(self, it, inputs, target, output, loss):
         self.values.append(loss.detach().clone())
+        if self.keep_output:
+            self.output = output
 
 
-def run_tbptt(dev, dist_mod, rows, steps, warmup, dtype, probe=True):
+DUMP_BUDGET_BYTES = 48 << 20      # of the 64 MB a dump may take
+
+
+def dump_sample_index(numel, cap, name):
+    """Flat indices of the stored entries of a `numel`-entry array called `name`: all of them
+    up to `cap`, else `cap` sorted draws (with replacement) from a generator seeded by the
+    name -- the same entries in every run and every build."""
+    if numel <= cap:
+        return None
+    import zlib
+    rng = np.random.Generator(np.random.PCG64(zlib.crc32(name.encode())))
+    return np.sort(rng.integers(0, numel, size=cap))
+
+
+def dump_outputs(dump_dir, pred, output, loss):
+    """Write the last timed step's results (see the module docstring) under dump_dir."""
+    arrays = [('loss', loss.reshape(1)), ('log_probs', output)]
+    rnns = pred.model.frame_level_rnns
+    arrays += [('hidden.%d' % i, pred.hidden_states[r]) for i, r in enumerate(rnns)
+               if pred.hidden_states.get(r) is not None]
+    arrays += [('param.' + k, p.detach()) for k, p in pred.named_parameters()]
+    # the largest per-array entry count at which the whole dump stays within the budget
+    left, cap = DUMP_BUDGET_BYTES // 4, None
+    for i, n in enumerate(sorted(t.numel() for _, t in arrays)):
+        cap = left // (len(arrays) - i)
+        if n > cap:
+            break
+        left -= n
+    os.makedirs(dump_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays:
+        flat = t.detach().reshape(-1)
+        idx = dump_sample_index(flat.numel(), cap, name)
+        if idx is not None:
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        a = flat.float().cpu().numpy()
+        np.save(os.path.join(dump_dir, name + '.npy'), a)
+        total += a.nbytes
+    log('dumped %d arrays, %.1f MB, to %s' % (len(arrays), total / 2 ** 20, dump_dir))
+
+
+def run_tbptt(dev, dist_mod, rows, steps, warmup, dtype, probe=True, dump_dir=None,
+              spare_chunks=0):
     """Warm-up then `steps` timed chunks of the drop-in Trainer.train on `rows` stream rows
     of this rank (graph mode: the warm-up runs the eager steps and the capture, the timed
     steps are replays).  Then, when `probe`, up to 5 more chunks run eagerly with the HIP-event
     probes around the kernel sites (per-kernel durations for the roofline; events cannot
-    time kernels inside a replayed graph) -- untimed for the headline value.  Returns a dict
-    (seconds = max over ranks)."""
+    time kernels inside a replayed graph) -- untimed for the headline value.  `dump_dir`:
+    right after the timed chunks, dump_outputs of the last one.  `spare_chunks`: the streams
+    are synthesised at least that many chunks longer than warm-up + timed (a stream is scaled
+    by its peak over its whole length, so the headline's inputs are the same with and without
+    the probe chunks only at the same length).  Returns a dict (seconds = max over ranks)."""
     import nn as snn
     import optim
     import samplernn_hip as H
@@ -192,10 +268,10 @@ def run_tbptt(dev, dist_mod, rows, steps, warmup, dtype, probe=True):
         if dist_mod.world() > 1 or os.environ.get('SRNN_DP_FORCE', '0') == '1' else None
     opt = optim.gradient_clipping(torch.optim.Adam(pred.parameters(), lr=1e-3), grad_sync=sync)
     n_probe = min(steps, 5) if probe else 0
-    batches = gpu_batches(synth_batches(rows, T, L, warmup + steps + n_probe,
-                                        dist_mod.rank() * rows), dev)
+    batches = synth_batches(rows, T, L, warmup + steps + max(n_probe, spare_chunks),
+                            dist_mod.rank() * rows, dev=dev)
     tr = Trainer(pred, snn.sequence_nll_loss_bits, opt, batches[:warmup], True, None)
-    log_ = _LossLog()
+    log_ = _LossLog(keep_output=dump_dir is not None)
     tr.register_plugin(log_)
     tr.train()                              # warm-up chunks (ends with the failure check)
     torch.cuda.synchronize()
@@ -213,9 +289,12 @@ def run_tbptt(dev, dist_mod, rows, steps, warmup, dtype, probe=True):
     enq = tr.enqueue_s
     replayed = tr.graph_steps - g0
     losses = [float(v) for v in log_.values]
+    if dump_dir is not None:
+        dump_outputs(dump_dir, pred, log_.output, log_.values[-1])
+        log_.output = None
     sites, eager_ms, eager_enq = {}, None, None
     if n_probe:
-        tr.dataset = batches[warmup + steps:]
+        tr.dataset = batches[warmup + steps:warmup + steps + n_probe]
         tr.enqueue_s = 0.0
         H.ROOF_EVENTS = {}
         t1 = time.perf_counter()
@@ -581,7 +660,14 @@ def main():
     ap.add_argument('--no-gen', action='store_true')
     ap.add_argument('--no-cpu', action='store_true')
     ap.add_argument('--no-extra', action='store_true', help='skip config_b / weak_64 lines')
+    ap.add_argument('--full', action='store_true',
+                    help='beside the headline: per-kernel roofline probes, the other '
+                         'configurations, generation and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the last timed step\'s outputs as DIR/<name>.npy')
     args = ap.parse_args()
+    if not args.full:       # a plain run measures the headline step and nothing else
+        args.no_extra = args.no_gen = args.no_cpu = True
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # not under torchrun: this process touches no GPU and runs N ranks as children
@@ -605,7 +691,9 @@ def main():
     if strong and GLOBAL_B % N:
         raise SystemExit('global batch %d not divisible by %d ranks' % (GLOBAL_B, N))
 
-    main_r = run_tbptt(dev, D, rows, args.steps, args.warmup, dtype)
+    main_r = run_tbptt(dev, D, rows, args.steps, args.warmup, dtype, probe=args.full,
+                       dump_dir=args.dump_outputs if D.rank() == 0 else None,
+                       spare_chunks=min(args.steps, 5))
     log('tbptt %d rows/GPU: %.2f ms/step (host enqueue %.2f ms/step, %d graph replays; eager '
         '%s ms/step), losses %s' % (
         rows, main_r['ms_per_step'], main_r['enqueue_ms_per_step'], main_r['graph_replays'],
@@ -664,7 +752,7 @@ def main():
             log('weak_64: %.2f ms/step' % r['ms_per_step'])
 
     gru = None
-    if args.dtype == 'bf16':
+    if args.full and args.dtype == 'bf16':
         gru = gru_sweep_roofline(dev, B=rows)
 
     def gen_line(dname, frame_sizes=(16, 4), cond_dim=43, n_cond=None, tag='3-tier dim1024 '

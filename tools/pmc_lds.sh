@@ -1,9 +1,9 @@
 #!/bin/bash
 # LDS-side counters of the L1 gather and the dTab scatter (one rocprofv3 --pmc pass of SQ
 # counters over a short B = 512 bench run): which of the wanted counters this ROCm lists, then
-# one pass with them, summarised per kernel -> gpurun_out/<TAG>_pmc_lds.txt
+# one pass with them, summarised per kernel -> bench_out/<TAG>_pmc_lds.txt
 set -e
-R=$PWD; O=$R/gpurun_out; mkdir -p $O; export TMPDIR=/tmp; cd /tmp
+R=$PWD; O=$R/bench_out; mkdir -p $O; export TMPDIR=/tmp; cd /tmp
 TAG=${TAG:-r05}
 timeout -s KILL 60 rocprofv3 -L > $O/${TAG}_rocprof_list.txt 2>&1 || true
 CTRS=$(python3 - "$O/${TAG}_rocprof_list.txt" <<'PY'
@@ -17,7 +17,7 @@ PY
 )
 echo "counters: $CTRS"
 rm -rf /tmp/plds
-timeout -s KILL 120 rocprofv3 --pmc $CTRS -d /tmp/plds -o run -- python3 $R/bench.py --steps 2 --warmup 2 --no-gen --no-cpu --no-extra --batch 512 > $O/${TAG}_pmc_lds_run.log 2>&1
+timeout -s KILL 120 rocprofv3 --pmc $CTRS -d /tmp/plds -o run -- python3 $R/bench.py --full --steps 2 --warmup 2 --no-gen --no-cpu --no-extra --batch 512 > $O/${TAG}_pmc_lds_run.log 2>&1
 python3 - $(find /tmp/plds -name '*.db' | head -1) > $O/${TAG}_pmc_lds.txt <<'PY'
 import sqlite3, sys
 c = sqlite3.connect(sys.argv[1])
