@@ -408,6 +408,9 @@ typedef struct SrnnModel {
  * shape on this device, or 0 when srnn_generate will use per-sample kernels instead.
  * Replaces nothing in the reference: a capability query for the Generator wrapper. */
 int srnn_gen_persistent_rows(int dtype, int n_seqs, int dim, int fs0, int q_levels);
+/* The same query for a call with sampling controls (srnn_generate3 given an array): the plan
+ * of the loop's controlled instantiation. */
+int srnn_gen_persistent_rows_ctrl(int dtype, int n_seqs, int dim, int fs0, int q_levels);
 /* Workspace bytes needed by srnn_generate for n_seqs rows. */
 int srnn_gen_workspace_size(const SrnnModel* m, int n_seqs, size_t* bytes);
 /* Generates n_cond * lookback samples for n_seqs rows.
@@ -431,6 +434,28 @@ int srnn_generate2(const SrnnModel* m, int n_seqs, int n_cond, const float* cond
                    const float* row_bias, const float* noise, uint64_t seed, int row0,
                    int64_t* seq, float* logp, void* workspace, size_t workspace_bytes, int flags,
                    void* stream);
+/* srnn_generate2 with per-row sampling controls.  Extends the draw of model.py:514-517
+ * (multinomial of the model's softmax: no temperature, no truncation) inside the same launches:
+ *   temperature (n_seqs) fp32 device array or NULL (= 1 for every row).  Domain: finite, >= 0.
+ *   top_k       (n_seqs) int32 device array or NULL (= off for every row).  Domain: [0, Q];
+ *               0 and Q both mean off.
+ * Per row b, with z the step's logits and q its noise (the same noise as without controls:
+ * Philox counters and the replayed `noise` indexing are unchanged):
+ *   S = {j : z_j >= v_k}, v_k the k-th largest logit (ties at v_k all kept; off: every j)
+ *   tau > 0:  x = argmax_{j in S} (z_j - tau log q_j)   (tau = 1, k off: srnn_generate2's draw,
+ *                                                        bit for bit)
+ *   tau = 0:  x = argmax_{j in S} z_j                    (greedy; the noise is not used)
+ * first index on ties.  The kernels do not validate: k outside [1, Q - 1] is treated as off and
+ * tau <= 0 (or NaN) as greedy; callers check the domain (model.sampling_controls does).
+ * `logp` stays the model's own log-softmax of z, not the tempered / truncated distribution.
+ * The arrays are read by every launch (and every graph replay): they must stay valid and
+ * unchanged until the call returns.  Both NULL: exactly srnn_generate2 (same kernels).  With
+ * either, the samplers' controlled instantiations run; the persistent loop's co-residency
+ * check is made on that instantiation.                                                    */
+int srnn_generate3(const SrnnModel* m, int n_seqs, int n_cond, const float* cond,
+                   const float* row_bias, const float* noise, uint64_t seed, int row0,
+                   int64_t* seq, float* logp, void* workspace, size_t workspace_bytes, int flags,
+                   void* stream, const float* temperature, const int32_t* top_k);
 
 #ifdef __cplusplus
 }

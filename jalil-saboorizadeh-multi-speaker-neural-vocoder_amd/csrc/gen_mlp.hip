@@ -247,7 +247,11 @@ __device__ __forceinline__ void gmt_grid_barrier(int* bar, int nblk, int epoch, 
 // masks of the runtime shape would otherwise be scalar-register spills in the loop.
 // TG: the bottom tick's GEMM runs in this launch before the sample loop (GenMlpArgs::tg;
 // bf16 only), with the prologue's resident-fragment loads in flight beside it.
-template <typename T, int UPW, int NT, int NZT, int MAXT, int FS0C, int DC, bool TG = false>
+// CT: the draw takes the rows' sampling controls (GenMlpArgs::temperature / top_k) -- builds
+// of their own, launched only when a control array is given: without one the kernels that run
+// are the plain ones, unchanged.
+template <typename T, int UPW, int NT, int NZT, int MAXT, int FS0C, int DC, bool TG = false,
+          bool CT = false>
 __global__ __launch_bounds__(gm::NTHR, 2) void gen_mlp_kernel(GenMlpArgs a) {
     using F = typename GmT<T>::frag;
     constexpr int GV = GmT<T>::GV, UK = GmT<T>::UK, EPL = UK / 4;
@@ -272,6 +276,11 @@ __global__ __launch_bounds__(gm::NTHR, 2) void gen_mlp_kernel(GenMlpArgs a) {
     // D + 8 floats (conflict-free ds_read_b128 B fragments), instead of in 32 VGPRs
     constexpr bool WOL = std::is_same<T, float>::value && UPW > 4;
     const T* wol = (const T*)((char*)gsh + 16);
+    // CT: the group's rows' sampling controls {tau, k} x 8 rows sit at the very end of the
+    // dynamic LDS (read once in the prologue: the loop holds neither array's pointer nor the
+    // values in registers -- it has none to spare -- and no other offset moves)
+    int* ctl = (int*)((char*)gsh + 16 + (WOL ? (size_t)NZ * (D + 8) * sizeof(T) : 0) +
+                      (TG ? (size_t)gmt::LDS : 0));
     const int p = blockIdx.x / a.G;
     const int c0 = p * CW, z0 = p * NZ;
     const int NU = (D + UK - 1) / UK;
@@ -293,7 +302,8 @@ __global__ __launch_bounds__(gm::NTHR, 2) void gen_mlp_kernel(GenMlpArgs a) {
                                   : nullptr;
 #define GM_W(k) do { if (dgw && s >= 2 && s < 5) dgw[(s - 2) * 16 + (k)] = __builtin_amdgcn_s_memrealtime(); } while (0)
     GM_STAMP();
-    // LDS: [tab15 Q x CW][red KW x ntm x 32 floatx4][hist R x HIST][words][W_out slice (WOL)]
+    // LDS: [tab15 Q x CW][red KW x ntm x 32 floatx4][hist R x HIST][words][W_out slice (WOL)
+    //      | tick GEMM ring (TG)][controls (CT)]
     T* tab15 = (T*)smem;
     size_t lo = ((size_t)Q * CW * sizeof(T) + 15) & ~(size_t)15;
     floatx4* red = (floatx4*)(smem + lo);
@@ -617,6 +627,14 @@ __global__ __launch_bounds__(gm::NTHR, 2) void gen_mlp_kernel(GenMlpArgs a) {
         const int j = i0 - FS0 + k;
         hist[r * gm::HIST + (j & (gm::HIST - 1))] = (int)a.seq[(int64_t)b * a.ldseq + j];
     }
+    if constexpr (CT) {
+        // the rows' controls (R <= 8: one a1 element per thread); a null array = its default
+        if (tid < min(R, 8)) {
+            const int b = min(g * R + tid, B - 1);
+            ctl[2 * tid] = (int)__float_as_uint(a.temperature ? a.temperature[b] : 1.0f);
+            ctl[2 * tid + 1] = a.top_k ? a.top_k[b] : 0;
+        }
+    }
     // this thread's a1/a2 element
     const bool own = tid < R * CW;
     // every wave's elements lie in the row that wave samples (r = wave)
@@ -634,10 +652,20 @@ __global__ __launch_bounds__(gm::NTHR, 2) void gen_mlp_kernel(GenMlpArgs a) {
         const float* gr = a.tk->G + (int64_t)tb * a.tk->ldg;
         const float* hr = a.tk->gh + (int64_t)tb * a.tk->ldgh;
         tg[0] = gr[tu]; tg[1] = gr[D + tu]; tg[2] = gr[2 * D + tu];
-        tg[3] = hr[tu]; tg[4] = hr[D + tu]; tg[5] = hr[2 * D + tu];
+        if constexpr (TG) {     // gh: this launch's GEMM output, written through by other
+                                // workgroups -- sc1 loads like every load of it (see below)
+            typedef __attribute__((address_space(1))) float gf;
+            gf* hw = (gf*)const_cast<float*>(hr);
+            tg[3] = __hip_atomic_load(hw + tu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            tg[4] = __hip_atomic_load(hw + D + tu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            tg[5] = __hip_atomic_load(hw + 2 * D + tu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        } else {
+            tg[3] = hr[tu]; tg[4] = hr[D + tu]; tg[5] = hr[2 * D + tu];
+        }
         tg[6] = a.tk->hp[(int64_t)tb * D + tu];
     };
-    if (!WOL && a.tk && tr < R && tb < B && tu < D) {
+    // (CT too: the controlled draw takes their place in the register budget)
+    if (!WOL && !CT && a.tk && tr < R && tb < B && tu < D) {
         const float* gr = a.tk->G + (int64_t)tb * a.tk->ldg;
         const float* hr = a.tk->gh + (int64_t)tb * a.tk->ldgh;
         tg[0] = gr[tu]; tg[1] = gr[D + tu]; tg[2] = gr[2 * D + tu];
@@ -881,7 +909,16 @@ __global__ __launch_bounds__(gm::NTHR, 2) void gen_mlp_kernel(GenMlpArgs a) {
             if (r == wave) GM_W(12);
             float* lrow = (p == 0 && valid && a.logp)
                               ? a.logp + ((int64_t)(i - a.L) * B + b) * Q : nullptr;
-            const int x = sample_row(v, lq, lrow, lane);
+            int x;
+            if constexpr (CT) {
+                // the row's controls, from LDS (tau scales log q at the point of use, so lq
+                // keeps its meaning whether drawn ahead or here)
+                const int rc = __builtin_amdgcn_readfirstlane(min(r, 7));
+                const int2 ck = *reinterpret_cast<const int2*>(ctl + 2 * rc);
+                x = sample_row_ctrl(v, lq, __uint_as_float((uint32_t)ck.x), ck.y, lrow, lane);
+            } else {
+                x = sample_row(v, lq, lrow, lane);
+            }
             if (lane == 0) {
                 hist[r * gm::HIST + (i & (gm::HIST - 1))] = x;
                 if (p == 0 && valid) a.seq[(int64_t)b * a.ldseq + i] = x;
@@ -907,7 +944,7 @@ __global__ __launch_bounds__(gm::NTHR, 2) void gen_mlp_kernel(GenMlpArgs a) {
         const GenMlpArgs::Tick* tk = a.tk;
         asm volatile("" : "+s"(tk));            // fresh loads of the table after the loop
         if (tr < R && tb < B && tu < D) {
-            if (WOL) load_tick();
+            if (WOL || CT) load_tick();
             const int inx = i0 + a.nsteps;
             const float* mr = tk->fmin + (int64_t)tu * 16;
             const float* mz = tk->fmin + (int64_t)(D + tu) * 16;
@@ -989,27 +1026,27 @@ __global__ void gen_wfrag_kernel(const char* __restrict__ w, int64_t ld_bytes, i
 namespace {
 typedef void (*GmKernel)(GenMlpArgs);
 
-template <typename T, int MAXT, int FS0C>
+template <typename T, int MAXT, int FS0C, bool CT>
 GmKernel pick_t(int upw, int nzt) {
-    if (upw <= 1 && nzt <= 16) return gen_mlp_kernel<T, 1, 4, 16, MAXT, FS0C, 0>;
-    if (upw <= 2 && nzt <= 4) return gen_mlp_kernel<T, 2, 4, 4, MAXT, FS0C, 0>;
-    if (upw <= 4 && nzt <= 2) return gen_mlp_kernel<T, 4, 4, 2, MAXT, FS0C, 0>;
+    if (upw <= 1 && nzt <= 16) return gen_mlp_kernel<T, 1, 4, 16, MAXT, FS0C, 0, false, CT>;
+    if (upw <= 2 && nzt <= 4) return gen_mlp_kernel<T, 2, 4, 4, MAXT, FS0C, 0, false, CT>;
+    if (upw <= 4 && nzt <= 2) return gen_mlp_kernel<T, 4, 4, 2, MAXT, FS0C, 0, false, CT>;
     return nullptr;     // other fp32 shapes at D > 512 would spill their resident weights
 }
-// MAXT = older taps gathered per sample (FS0 - 1 <= MAXT)
-template <typename T>
+// MAXT = older taps gathered per sample (FS0 - 1 <= MAXT); CT = the sampling-control builds
+template <typename T, bool CT>
 GmKernel pick(int upw, int nzt, int fs0, int D, int R) {
     // (FS0 = 16, the bottom frame of every published config, gets its own build: a
     //  constant FS0 folds the tap bookkeeping that would otherwise live in scalar registers;
     //  dim 1024 in bf16 -- the published model -- has its whole launch shape compiled in)
     if (std::is_same<T, bf16>::value && fs0 == 16 && D == 1024 && R == 8)
-        return gen_mlp_kernel<T, 4, 4, 2, 15, 16, 1024>;
+        return gen_mlp_kernel<T, 4, 4, 2, 15, 16, 1024, false, CT>;
     // fp32 at dim 1024 (the reference's precision): 8 K units per wave, one 16-logit tile
     // whose W_out rows sit in LDS (WOL)
     if (std::is_same<T, float>::value && fs0 == 16 && D == 1024 && R == 8)
-        return gen_mlp_kernel<T, 8, 4, 1, 15, 16, 1024>;
-    if (fs0 == 16) return pick_t<T, 15, 16>(upw, nzt);
-    return fs0 - 1 <= 15 ? pick_t<T, 15, 0>(upw, nzt) : pick_t<T, 31, 0>(upw, nzt);
+        return gen_mlp_kernel<T, 8, 4, 1, 15, 16, 1024, false, CT>;
+    if (fs0 == 16) return pick_t<T, 15, 16, CT>(upw, nzt);
+    return fs0 - 1 <= 15 ? pick_t<T, 15, 0, CT>(upw, nzt) : pick_t<T, 31, 0, CT>(upw, nzt);
 }
 
 int device_cus() {
@@ -1024,7 +1061,7 @@ int device_cus() {
 }
 }  // namespace
 
-int gen_mlp_plan(int dtype, int B, int D, int FS0, int Q, GenMlpPlan* pl) {
+int gen_mlp_plan(int dtype, int B, int D, int FS0, int Q, int ctrl, GenMlpPlan* pl) {
     memset(pl, 0, sizeof(*pl));
     if (Q != gm::Q || FS0 < 1 || FS0 > gm::HIST || D % 16 || D > 1024 || B < 1) return 0;
     const int CW = D < 64 ? D : 64;
@@ -1040,8 +1077,13 @@ int gen_mlp_plan(int dtype, int B, int D, int FS0, int Q, GenMlpPlan* pl) {
         // every workgroup co-resident, for each process sharing the device (persist.hip)
         if (srnn_persist_fits_cus((int64_t)cdiv(B, r) * P)) { R = r; break; }
     if (!R) return 0;
-    const GmKernel k = dtype == SRNN_BF16 ? pick<bf16>(upw, NZ / 16, FS0, D, R)
-                                          : pick<float>(upw, NZ / 16, FS0, D, R);
+    // (the kernels recorded here are the ones gen_mlp_launch starts and asks the occupancy
+    //  of: with controls, their own instantiations)
+    const GmKernel k = dtype == SRNN_BF16
+                           ? (ctrl ? pick<bf16, true>(upw, NZ / 16, FS0, D, R)
+                                   : pick<bf16, false>(upw, NZ / 16, FS0, D, R))
+                           : (ctrl ? pick<float, true>(upw, NZ / 16, FS0, D, R)
+                                   : pick<float, false>(upw, NZ / 16, FS0, D, R));
     if (!k) return 0;
     // the in-launch tick GEMM variant (bf16, the compiled D = 1024 / FS0 = 16 shape);
     // SRNN_GEN_TICK_GEMM=0 keeps the bottom tick's GEMM a launch of its own
@@ -1049,7 +1091,9 @@ int gen_mlp_plan(int dtype, int B, int D, int FS0, int Q, GenMlpPlan* pl) {
     pl->lds_tg = 0;
     if (dtype == SRNN_BF16 && FS0 == 16 && D == 1024 && R == 8 && Q == gm::Q &&
         env_flag("SRNN_GEN_TICK_GEMM", 1))
-        pl->kernel_tg = (const void*)gen_mlp_kernel<bf16, 4, 4, 2, 15, 16, 1024, true>;
+        pl->kernel_tg =
+            ctrl ? (const void*)gen_mlp_kernel<bf16, 4, 4, 2, 15, 16, 1024, true, true>
+                 : (const void*)gen_mlp_kernel<bf16, 4, 4, 2, 15, 16, 1024, true>;
     const int es = dtype == SRNN_BF16 ? 2 : 4;
     const int KW = NU < gm::NW ? NU : gm::NW;
     const int ntm = (CW / 16) > (NZ / 16) ? CW / 16 : NZ / 16;
@@ -1057,6 +1101,7 @@ int gen_mlp_plan(int dtype, int B, int D, int FS0, int Q, GenMlpPlan* pl) {
     lds += (size_t)KW * ntm * 32 * 16;                // rows 0..7 of the 16-row tiles (R = 8)
     lds += (size_t)R * gm::HIST * 4;
     lds += 16;                                        // group / member / mode words
+    if (ctrl) lds += 64;                              // the rows' controls (gen_mlp_kernel CT)
     if (dtype == SRNN_F32 && upw > 4)                 // W_out slice in LDS (gen_mlp_kernel WOL)
         lds += (size_t)NZ * (D + 8) * 4;
     if (lds > 160 * 1024) return 0;
@@ -1067,6 +1112,7 @@ int gen_mlp_plan(int dtype, int B, int D, int FS0, int Q, GenMlpPlan* pl) {
     pl->ok = 1;
     pl->local = env_flag("SRNN_GEN_LOCAL", 1);
     pl->dtype = dtype;
+    pl->ctrl = ctrl ? 1 : 0;
     pl->R = R;
     pl->G = cdiv(B, R);
     pl->P = P;
@@ -1176,6 +1222,8 @@ int gen_mlp_launch(const GenMlpPlan* pl, GenMlpArgs a, hipStream_t s) {
     // SRNN_GEN_LOCAL=0 only forces the global-mode hand-offs
     SRNN_REQUIRE(a.census && pl->G * pl->P <= HX_KEYED_WORDS, "gen_mlp: no census array");
     a.nolocal = pl->local ? 0 : 1;
+    SRNN_REQUIRE((pl->ctrl != 0) == (a.temperature || a.top_k),
+                 "gen_mlp: plan and sampling-control arrays disagree");
     {
         // SRNN_GEN_DIAG=1: phase timestamps of the first launch into a device buffer that
         // srnn_gen_diag_dump prints (timing diagnostics only)
@@ -1204,14 +1252,14 @@ int gen_mlp_launch(const GenMlpPlan* pl, GenMlpArgs a, hipStream_t s) {
     const GmKernel k = (GmKernel)(tg ? pl->kernel_tg : pl->kernel);
     const size_t lds = tg ? pl->lds_tg : pl->lds;
     // raise the dynamic-LDS limit once per kernel (not inside a graph capture's launches)
-    static const void* done[16];
-    static size_t done_lds[16];
+    static const void* done[64];
+    static size_t done_lds[64];
     int slot = 0;
-    while (slot < 16 && done[slot] && done[slot] != (const void*)k) ++slot;
-    if (slot == 16 || !done[slot] || done_lds[slot] < lds) {
+    while (slot < 64 && done[slot] && done[slot] != (const void*)k) ++slot;
+    if (slot == 64 || !done[slot] || done_lds[slot] < lds) {
         SRNN_CHECK_HIP(hipFuncSetAttribute((const void*)k,
                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        if (slot < 16) { done[slot] = (const void*)k; done_lds[slot] = 160 * 1024; }
+        if (slot < 64) { done[slot] = (const void*)k; done_lds[slot] = 160 * 1024; }
     }
     if (srnn_persist_check((const void*)k, gm::NTHR, lds, (int64_t)pl->G * pl->P, "gen_mlp"))
         return 1;

@@ -24,7 +24,7 @@ int srnn_mlp_l1_impl(int dtype, const void* tab, const int64_t* x, int64_t ldx, 
 int srnn_sample_impl(const float* z, int64_t ldz, int B, const float* noise, uint64_t seed,
                      int row0,
                      const int* base, int off, int L, int64_t* seq, int64_t ldseq,
-                     float* logp_out, hipStream_t s);
+                     float* logp_out, const float* temperature, const int* top_k, hipStream_t s);
 int srnn_gru_cell_impl(int dtype, int B, int D, int Din, const void* x, int64_t ldx,
                        const void* wih, const float* bih, const float* gi, int64_t ldgi,
                        const void* h, int64_t ldh, const float* hf, int64_t ldhf, const void* whh,
@@ -463,6 +463,8 @@ struct Ctx {
     int64_t* seq;
     int64_t ldseq;
     float* logp;
+    const float* temperature = nullptr;   // per-row sampling controls (device, n_seqs), or null
+    const int* top_k = nullptr;
     hipStream_t s;
     const GenMlpPlan* pl;     // persistent sample loop, or null for per-sample kernels
     // lq holds the draws of block-relative steps [noise_beg, noise_end): drawn ahead by the
@@ -658,7 +660,7 @@ int mlp_step(Ctx& c, int off) {
     RET(linear_fwd(dt, SRNN_F32, B, Q, D, c.b.a2, D, m->w_out, D, m->b_out, c.b.logits, Q, 0,
                    c.s));
     RET(srnn_sample_impl(c.b.logits, Q, B, c.noise, c.seed, c.row0, c.b.base, off, c.L, c.seq, c.ldseq,
-                         c.logp, c.s));
+                         c.logp, c.temperature, c.top_k, c.s));
     return 0;
 }
 
@@ -691,6 +693,7 @@ int run_block(Ctx& c, int periods) {
             a.B = c.B; a.D = m->dim; a.FS0 = m->tier[0].frame_size;
             a.xa1 = c.b.xa1; a.xa2 = c.b.xa2; a.xz = c.b.xz; a.err = c.b.gerr;
             a.census = c.b.gerr + 64;
+            a.temperature = c.temperature; a.top_k = c.top_k;
             if (c.b.lq && env_flag("SRNN_GEN_NOISE_AHEAD", 1)) {
                 // drawn ahead by a tick's input launch, else by a launch here
                 if (off < c.noise_beg || off + a.nsteps > c.noise_end) {
@@ -725,15 +728,25 @@ int run_block(Ctx& c, int periods) {
 }  // namespace
 
 // persistent sample loop plan for this model/batch (ok = 0: per-sample kernels)
-static void plan_for(const SrnnModel* m, int n_seqs, GenMlpPlan* pl) {
-    if (!gen_mlp_plan(m->dtype, n_seqs, m->dim, m->tier[0].frame_size, m->q_levels, pl) ||
+static void plan_for(const SrnnModel* m, int n_seqs, int ctrl, GenMlpPlan* pl) {
+    if (!gen_mlp_plan(m->dtype, n_seqs, m->dim, m->tier[0].frame_size, m->q_levels, ctrl, pl) ||
         !env_flag("SRNN_GEN_PERSIST", 1))
         pl->ok = 0;
 }
 
 extern "C" int srnn_gen_persistent_rows(int dtype, int n_seqs, int dim, int fs0, int q_levels) {
     GenMlpPlan pl;
-    if (!gen_mlp_plan(dtype, n_seqs, dim, fs0, q_levels, &pl) || !env_flag("SRNN_GEN_PERSIST", 1))
+    if (!gen_mlp_plan(dtype, n_seqs, dim, fs0, q_levels, 0, &pl) || !env_flag("SRNN_GEN_PERSIST", 1))
+        return 0;
+    return pl.R;
+}
+
+// the same for a call with sampling controls (srnn_generate3 with an array): the controlled
+// instantiation's plan, which takes 64 B more LDS
+extern "C" int srnn_gen_persistent_rows_ctrl(int dtype, int n_seqs, int dim, int fs0,
+                                             int q_levels) {
+    GenMlpPlan pl;
+    if (!gen_mlp_plan(dtype, n_seqs, dim, fs0, q_levels, 1, &pl) || !env_flag("SRNN_GEN_PERSIST", 1))
         return 0;
     return pl.R;
 }
@@ -742,28 +755,41 @@ extern "C" int srnn_gen_workspace_size(const SrnnModel* m, int n_seqs, size_t* b
     SRNN_REQUIRE(m && bytes && n_seqs > 0, "gen_workspace_size: bad args");
     Bufs b;
     GenMlpPlan pl;
-    plan_for(m, n_seqs, &pl);
+    plan_for(m, n_seqs, 0, &pl);      // (the workspace does not depend on the controls)
     *bytes = carve(m, n_seqs, nullptr, &b, &pl);
     return 0;
 }
 
-extern "C" int srnn_generate2(const SrnnModel* m, int n_seqs, int n_cond, const float* cond,
+extern "C" int srnn_generate3(const SrnnModel* m, int n_seqs, int n_cond, const float* cond,
                               const float* row_bias, const float* noise, uint64_t seed,
                               int row0, int64_t* seq, float* logp, void* workspace,
-                              size_t workspace_bytes, int flags, void* stream);
+                              size_t workspace_bytes, int flags, void* stream,
+                              const float* temperature, const int32_t* top_k);
 
 extern "C" int srnn_generate(const SrnnModel* m, int n_seqs, int n_cond, const float* cond,
                              const float* row_bias, const float* noise, uint64_t seed,
                              int64_t* seq, float* logp, void* workspace, size_t workspace_bytes,
                              int flags, void* stream) {
-    return srnn_generate2(m, n_seqs, n_cond, cond, row_bias, noise, seed, 0, seq, logp,
-                          workspace, workspace_bytes, flags, stream);
+    return srnn_generate3(m, n_seqs, n_cond, cond, row_bias, noise, seed, 0, seq, logp,
+                          workspace, workspace_bytes, flags, stream, nullptr, nullptr);
 }
 
 extern "C" int srnn_generate2(const SrnnModel* m, int n_seqs, int n_cond, const float* cond,
                               const float* row_bias, const float* noise, uint64_t seed,
                               int row0, int64_t* seq, float* logp, void* workspace,
                               size_t workspace_bytes, int flags, void* stream) {
+    return srnn_generate3(m, n_seqs, n_cond, cond, row_bias, noise, seed, row0, seq, logp,
+                          workspace, workspace_bytes, flags, stream, nullptr, nullptr);
+}
+
+// srnn_generate2 with per-row sampling controls (sampler.hpp sample_row_ctrl): with both
+// arrays null every launch is the plain one; with either, the sampler kernels' controlled
+// instantiations run (the persistent loop's own build, planned and checked as such).
+extern "C" int srnn_generate3(const SrnnModel* m, int n_seqs, int n_cond, const float* cond,
+                              const float* row_bias, const float* noise, uint64_t seed,
+                              int row0, int64_t* seq, float* logp, void* workspace,
+                              size_t workspace_bytes, int flags, void* stream,
+                              const float* temperature, const int32_t* top_k) {
     SRNN_REQUIRE(row0 >= 0, "generate: negative row offset");
     SRNN_REQUIRE(m && n_seqs > 0 && n_cond > 0 && seq && workspace, "generate: bad args");
     SRNN_REQUIRE(m->n_tiers >= 1 && m->n_tiers <= SRNN_MAX_TIERS, "generate: n_tiers");
@@ -773,7 +799,7 @@ extern "C" int srnn_generate2(const SrnnModel* m, int n_seqs, int n_cond, const 
     Ctx c;
     c.m = m;
     GenMlpPlan pl;
-    plan_for(m, n_seqs, &pl);
+    plan_for(m, n_seqs, (temperature || top_k) ? 1 : 0, &pl);
     if (flags & 2) pl.ok = 0;          // caller asked for the per-sample kernel path
     size_t need = carve(m, n_seqs, (char*)workspace, &c.b, &pl);
     SRNN_REQUIRE(workspace_bytes >= need, "generate: workspace %zu < %zu", workspace_bytes, need);
@@ -788,6 +814,8 @@ extern "C" int srnn_generate2(const SrnnModel* m, int n_seqs, int n_cond, const 
     c.seq = seq;
     c.ldseq = (int64_t)c.L * (n_cond + 1);
     c.logp = logp;
+    c.temperature = temperature;
+    c.top_k = top_k;
     c.pl = pl.ok ? &pl : nullptr;
     c.tick_gemm = c.pl && c.b.fold &&
                   gen_mlp_tick_gemm_ok(&pl, (m->tier[0].frame_size + 3) * m->dim, m->dim, n_seqs);

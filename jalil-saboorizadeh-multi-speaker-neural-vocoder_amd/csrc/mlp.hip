@@ -614,10 +614,14 @@ extern "C" int srnn_nll_bwd(const int64_t* target, int64_t ldt, int Tlen, int64_
 // ------------------------------------------------------------------ sampler
 // One wave per row; lane holds q = 4 * lane + j (16-B loads of logits and noise).  The
 // per-row math lives in sampler.hpp, shared with the persistent generation loop.
+// CT: the row's sampling controls (temperature[b], top_k[b]; either array may be null = that
+// control at its default) go into the draw; without them the kernel is the plain sampler.
+template <bool CT>
 __global__ __launch_bounds__(256) void sample_kernel(
     const float* __restrict__ z, int64_t ldz, int B, const float* __restrict__ noise,
     uint64_t seed, int row0, const int* __restrict__ base, int off, int L,
-    int64_t* __restrict__ seq, int64_t ldseq, float* __restrict__ logp_out) {
+    int64_t* __restrict__ seq, int64_t ldseq, float* __restrict__ logp_out,
+    const float* __restrict__ temperature, const int* __restrict__ top_k) {
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (b >= B) return;
@@ -625,16 +629,26 @@ __global__ __launch_bounds__(256) void sample_kernel(
     const int step = i - L;
     const floatx4 v = *reinterpret_cast<const floatx4*>(z + (int64_t)b * ldz + 4 * lane);
     const floatx4 lq = log_noise(sample_noise(noise, seed, B, b, step, lane, row0));
-    const int bi = sample_row(v, lq, logp_out ? logp_out + ((int64_t)step * B + b) * 256 : nullptr,
-                              lane);
+    float* lrow = logp_out ? logp_out + ((int64_t)step * B + b) * 256 : nullptr;
+    int bi;
+    if constexpr (CT)
+        bi = sample_row_ctrl(v, lq, temperature ? temperature[b] : 1.0f, top_k ? top_k[b] : 0,
+                             lrow, lane);
+    else
+        bi = sample_row(v, lq, lrow, lane);
     if (lane == 0) seq[(int64_t)b * ldseq + i] = bi;
 }
 
 int srnn_sample_impl(const float* z, int64_t ldz, int B, const float* noise, uint64_t seed,
                      int row0, const int* base, int off, int L, int64_t* seq, int64_t ldseq,
-                     float* logp_out, hipStream_t s) {
-    hipLaunchKernelGGL(sample_kernel, dim3(cdiv(B, 4)), dim3(256), 0, s, z, ldz, B, noise, seed,
-                       row0, base, off, L, seq, ldseq, logp_out);
+                     float* logp_out, const float* temperature, const int* top_k, hipStream_t s) {
+    if (temperature || top_k)
+        hipLaunchKernelGGL(sample_kernel<true>, dim3(cdiv(B, 4)), dim3(256), 0, s, z, ldz, B, noise,
+                           seed, row0, base, off, L, seq, ldseq, logp_out, temperature, top_k);
+    else
+        hipLaunchKernelGGL(sample_kernel<false>, dim3(cdiv(B, 4)), dim3(256), 0, s, z, ldz, B,
+                           noise, seed, row0, base, off, L, seq, ldseq, logp_out, temperature,
+                           top_k);
     SRNN_LAUNCH_CHECK();
     return 0;
 }

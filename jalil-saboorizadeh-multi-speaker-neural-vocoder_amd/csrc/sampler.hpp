@@ -102,11 +102,38 @@ __device__ __forceinline__ floatx4 log_noise(const floatx4& q) {
     return floatx4{logf(q[0]), logf(q[1]), logf(q[2]), logf(q[3])};
 }
 
+// The two halves of a row's draw as sample_row_ctrl uses them (sample_row below spells out
+// the same operations: for identical scores every kernel returns the same index).
+// Index of the largest of the row's 256 scores t (lane holds 4 lane + j), first index on ties.
+__device__ __forceinline__ int row_argmax(const floatx4& t, int lane) {
+    float best = t[0];
+    int bi = 4 * lane;
+#pragma unroll
+    for (int j = 1; j < 4; ++j) {
+        if (t[j] > best) { best = t[j]; bi = 4 * lane + j; }
+    }
+    return __builtin_amdgcn_readfirstlane(wave_argmax(best, bi));
+}
+// log_softmax of the row's logits v to logp_row
+__device__ __forceinline__ void row_logp(const floatx4& v, float* logp_row, int lane) {
+    float m = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
+    m = wave_max(m);
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s += expf(v[j] - m);
+    s = wave_sum(s);
+    const float ls = logf(s);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) logp_row[4 * lane + j] = (v[j] - m) - ls;
+}
+
 // One wave, one row of Q = 256 logits (lane holds q = 4 lane + j), lq = log_noise(q).
 // Returns the sampled index (wave-uniform); writes the row's log-probs to logp_row (if
 // non-null).  The draw argmax_j softmax(z)_j / q_j (model.py:514) is taken in log space as
 // argmax_j (z_j - log q_j): the softmax normaliser is common to all j, so the index needs no
 // reduction but the argmax (first index on ties); log-probs, when asked for, come after.
+// (Kept in its own words, not as a call of the two halves above: the persistent loop's plain
+//  builds are register-exact as they are.  Same operations in the same order.)
 __device__ __forceinline__ int sample_row(const floatx4& v, const floatx4& lq, float* logp_row,
                                           int lane) {
     float best = v[0] - lq[0];
@@ -128,5 +155,74 @@ __device__ __forceinline__ int sample_row(const floatx4& v, const floatx4& lq, f
 #pragma unroll
         for (int j = 0; j < 4; ++j) logp_row[4 * lane + j] = (v[j] - m) - ls;
     }
+    return bi;
+}
+
+// ---- sampling controls: temperature and top-k, per row ----------------------------------
+// Extends the draw of model.py:514-517 (which has neither) in the same log-space form:
+//   S = {j : z_j >= v_k}, v_k the k-th largest logit of the row (ties at v_k all kept);
+//       k outside [1, Q - 1] is "off": S is every j
+//   tau > 0:   x = argmax_{j in S} (z_j - tau log q_j)   (fp32: one fma; at tau = 1 it is
+//              z_j - log q_j to the bit, so a default row draws sample_row's index)
+//   tau <= 0:  x = argmax_{j in S} z_j                    (greedy; the noise is not read)
+// first index on ties in both.  The log-probs stay the model's own log_softmax(z).
+
+// Order-preserving unsigned key of a float and its inverse: a < b => key(a) < key(b), the
+// bits come back exactly (-0 keeps its own key, just below +0's)
+__device__ __forceinline__ uint32_t float_key(float v) {
+    const uint32_t u = __float_as_uint(v);
+    return u ^ ((uint32_t)((int32_t)u >> 31) | 0x80000000u);
+}
+__device__ __forceinline__ float key_float(uint32_t key) {
+    return __uint_as_float(key ^ (~(uint32_t)((int32_t)key >> 31) | 0x80000000u));
+}
+
+// Key of the k-th largest (1 <= k <= 256) of a row's 256 keys (4 per lane), wave-uniform, no
+// LDS: the largest t with |{key >= t}| >= k, found bit by bit from the top.  Each of the 32
+// steps is 4 compares into lane masks, 4 scalar popcounts and a scalar select; there is no
+// early exit (every lane runs all 32 steps) and nothing to wait for.  All 64 lanes must be
+// active.
+__device__ __forceinline__ uint32_t wave_kth_largest_key(const uint32_t (&key)[4], int k) {
+    uint32_t t = 0;
+#pragma unroll
+    for (int bit = 31; bit >= 0; --bit) {
+        const uint32_t c = t | (1u << bit);
+        const int n = __popcll(__ballot(key[0] >= c)) + __popcll(__ballot(key[1] >= c)) +
+                      __popcll(__ballot(key[2] >= c)) + __popcll(__ballot(key[3] >= c));
+        t = n >= k ? c : t;
+    }
+    return t;
+}
+
+// sample_row with the row's controls (tau, k wave-uniform).  The select comes first and is
+// skipped by a wave-uniform branch when k is off.  It holds the row as keys IN PLACE of the
+// logits (which are rebuilt from them afterwards, bit for bit), so no more values are live
+// across it than across the plain draw: the persistent loop has no registers to spare.  The
+// allowed set is then the float compare z_j >= v_k (which also keeps -0 with +0).
+__device__ __forceinline__ int sample_row_ctrl(const floatx4& v, const floatx4& lq, float tau,
+                                               int k, float* logp_row, int lane) {
+    tau = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(tau)));
+    k = __builtin_amdgcn_readfirstlane(k);
+    floatx4 z = v;
+    float vk = -__builtin_inff();
+    if (k >= 1 && k <= 255) {
+        uint32_t key[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) key[j] = float_key(z[j]);
+        // (opaque to the compiler, or it would keep the logits live beside their keys)
+        asm volatile("" : "+v"(key[0]), "+v"(key[1]), "+v"(key[2]), "+v"(key[3]));
+        vk = key_float(wave_kth_largest_key(key, k));
+#pragma unroll
+        for (int j = 0; j < 4; ++j) z[j] = key_float(key[j]);
+    }
+    floatx4 t;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        // (tau <= 0: greedy, the noise is not read -- log q may be -inf)
+        const float sc = tau > 0.f ? __builtin_fmaf(-tau, lq[j], z[j]) : z[j];
+        t[j] = z[j] >= vk ? sc : -__builtin_inff();
+    }
+    const int bi = row_argmax(t, lane);
+    if (logp_row) row_logp(z, logp_row, lane);
     return bi;
 }

@@ -14,6 +14,7 @@ The drop-in classes call these ops, so the registered ops ARE the product path:
   srnn::adam_clip_              gradient_clipping + Adam (optim.py:4-21), in place
   srnn::step_advance_           the device step counters srnn::adam_clip_ can read (graph mode)
   srnn::generate                Generator.__call__'s sample loop (model.py:445-520)
+  srnn::generate_ctrl           the same loop with per-row temperature / top-k in the draw
 
 Every op has a fake (meta) kernel, so FakeTensor / torch.compile tracing sees shapes without
 running HIP code, and the differentiable ones have their autograd formula attached with
@@ -396,13 +397,8 @@ def _(dstep):
 
 
 # ------------------------------------------------------------------ generation
-@torch.library.custom_op('srnn::generate', mutates_args=())
-def generate(weights: list[Tensor], meta: list[int], cond: Tensor, row_bias: Tensor,
-             noise: Optional[Tensor], seed: int, row_offset: int, flags: int,
-             return_logp: bool) -> tuple[Tensor, Tensor]:
-    """The whole autoregressive loop (model.py:445-520) on the device: (sample indices
-    (n_seqs, L + T) int64, per-step log-probs (T, n_seqs, Q) or empty).  weights / meta:
-    model.generation_weights' tensors and layout."""
+def _generate(weights, meta, cond, row_bias, noise, seed, row_offset, flags, return_logp,
+              temperature=None, top_k=None):
     import ctypes
     import model
     m = model.srnn_model_struct(weights, meta)
@@ -416,15 +412,17 @@ def generate(weights: list[Tensor], meta: list[int], cond: Tensor, row_bias: Ten
     sz = ctypes.c_size_t(0)
     H.lib().call('srnn_gen_workspace_size', ctypes.byref(m), n_seqs, ctypes.byref(sz))
     ws = torch.empty(sz.value, device=dev, dtype=torch.uint8)
-    H.lib().call('srnn_generate2', ctypes.byref(m), n_seqs, num_cond, H.ptr(cond),
-                 H.ptr(row_bias), H.ptr(noise), int(seed) & ((1 << 64) - 1), int(row_offset),
-                 H.ptr(seq), H.ptr(logp) if return_logp else None, H.ptr(ws), sz.value,
-                 int(flags), H.stream())
+    args = (ctypes.byref(m), n_seqs, num_cond, H.ptr(cond), H.ptr(row_bias), H.ptr(noise),
+            int(seed) & ((1 << 64) - 1), int(row_offset), H.ptr(seq),
+            H.ptr(logp) if return_logp else None, H.ptr(ws), sz.value, int(flags), H.stream())
+    if temperature is None and top_k is None:
+        H.lib().call('srnn_generate2', *args)
+    else:
+        H.lib().call('srnn_generate3', *args, H.ptr(temperature), H.ptr(top_k))
     return seq, logp
 
 
-@generate.register_fake
-def _(weights, meta, cond, row_bias, noise, seed, row_offset, flags, return_logp):
+def _generate_fake(meta, cond, return_logp):
     n_seqs, num_cond = cond.shape[0], cond.shape[1]
     L = meta[-1]
     Q = meta[3]                      # q_levels (model.generation_weights' meta layout)
@@ -433,5 +431,44 @@ def _(weights, meta, cond, row_bias, noise, seed, row_offset, flags, return_logp
             cond.new_empty((T, n_seqs, Q) if return_logp else (0,)))
 
 
+@torch.library.custom_op('srnn::generate', mutates_args=())
+def generate(weights: list[Tensor], meta: list[int], cond: Tensor, row_bias: Tensor,
+             noise: Optional[Tensor], seed: int, row_offset: int, flags: int,
+             return_logp: bool) -> tuple[Tensor, Tensor]:
+    """The whole autoregressive loop (model.py:445-520) on the device: (sample indices
+    (n_seqs, L + T) int64, per-step log-probs (T, n_seqs, Q) or empty).  weights / meta:
+    model.generation_weights' tensors and layout."""
+    return _generate(weights, meta, cond, row_bias, noise, seed, row_offset, flags, return_logp)
+
+
+@generate.register_fake
+def _(weights, meta, cond, row_bias, noise, seed, row_offset, flags, return_logp):
+    return _generate_fake(meta, cond, return_logp)
+
+
+@torch.library.custom_op('srnn::generate_ctrl', mutates_args=())
+def generate_ctrl(weights: list[Tensor], meta: list[int], cond: Tensor, row_bias: Tensor,
+                  noise: Optional[Tensor], seed: int, row_offset: int, flags: int,
+                  return_logp: bool, temperature: Tensor, top_k: Tensor) -> tuple[Tensor, Tensor]:
+    """srnn::generate with per-row sampling controls in the draw (srnn_generate3):
+    temperature (n_seqs,) float32, finite and >= 0 (0 = greedy); top_k (n_seqs,) int32 in
+    [0, Q] (0 and Q = off).  model.sampling_controls validates and builds both.  The returned
+    log-probs stay the model's own log-softmax, not the tempered / truncated distribution."""
+    n_seqs = cond.shape[0]
+    for name, t, dt in (('temperature', temperature, torch.float32), ('top_k', top_k, torch.int32)):
+        if (t.dtype != dt or t.dim() != 1 or t.shape[0] != n_seqs or not t.is_contiguous() or
+                t.device != cond.device):
+            raise ValueError('generate_ctrl: %s must be a contiguous (%d,) %s tensor on %s'
+                             % (name, n_seqs, dt, cond.device))
+    return _generate(weights, meta, cond, row_bias, noise, seed, row_offset, flags, return_logp,
+                     temperature, top_k)
+
+
+@generate_ctrl.register_fake
+def _(weights, meta, cond, row_bias, noise, seed, row_offset, flags, return_logp, temperature,
+      top_k):
+    return _generate_fake(meta, cond, return_logp)
+
+
 OPS = ('tier_fwd', 'tier_bwd', 'mlp_fwd', 'mlp_bwd', 'nll_bits', 'nll_bits_bwd', 'upsample',
-       'upsample_bwd', 'dequant', 'adam_clip_', 'step_advance_', 'generate')
+       'upsample_bwd', 'dequant', 'adam_clip_', 'step_advance_', 'generate', 'generate_ctrl')

@@ -15,6 +15,11 @@ Two sampling modes:
   * --sampler philox --batch_files true: every file of the list in ONE device call (rows =
     files x n_samples, conditioning zero-padded to the longest file, outputs trimmed to each
     file's own length -- rows never interact), noise from the on-device Philox generator.
+
+Beyond the reference: --temperature T (default 1.0) and --top_k K (default 0 = off) set the
+Generator's sampling controls for every row of every call -- the draw becomes
+argmax(z - T log q) over the K largest logits; --temperature 0 is greedy (no randomness).
+At the defaults the run is the reference's draw, bit for bit as before.
 """
 import argparse
 import os
@@ -59,6 +64,8 @@ default_params = {
     'sampler': 'torch',
     'batch_files': False,
     'compute_dtype': 'fp32',
+    'temperature': 1.0,
+    'top_k': 0,
 }
 
 
@@ -176,6 +183,7 @@ def main(frame_sizes, **params):
             rows[j * n:(j + 1) * n, :c.shape[0]] = c
             spks[j * n:(j + 1) * n] = jobs[j][1]
         gen = Generator(model, use_cuda)
+        ctrl = dict(temperature=params['temperature'], top_k=params['top_k'])
         if world > 1:
             # rank-sharded: contiguous row shards gathered at the end (rows
             # padded to a multiple of the world size); either sampler reproduces the
@@ -185,10 +193,10 @@ def main(frame_sizes, **params):
             pspk = np.concatenate([spks, np.zeros(pad, spks.dtype)])
             out = shard_generate(gen, len(prow), prow, pspk, params['seed'],
                                  sampler=params['sampler'], noise_rows=len(rows),
-                                 seq_len=params['sample_length']).numpy()[:len(rows)]
+                                 seq_len=params['sample_length'], **ctrl).numpy()[:len(rows)]
         else:
             out = gen(len(rows), params['sample_length'], rows, spks, sampler=params['sampler'],
-                      seed=params['seed']).numpy()
+                      seed=params['seed'], **ctrl).numpy()
         if rank != 0:
             return
         L = model.lookback
@@ -207,7 +215,8 @@ def main(frame_sizes, **params):
         print('Generating file', fname)
         gen = Generator(model, use_cuda)
         samples = gen(params['n_samples'], params['sample_length'], cond, speaker,
-                      sampler=params['sampler'], seed=params['seed']).numpy()
+                      sampler=params['sampler'], seed=params['seed'],
+                      temperature=params['temperature'], top_k=params['top_k']).numpy()
         for i in range(params['n_samples']):
             write_wav(fname, samples[i, :], sr=params['sample_rate'])
 
@@ -235,7 +244,8 @@ def build_parser():
                       ('norm_ind', parse_bool), ('look_ahead', float),
                       ('static_spk', parse_bool), ('seed', int), ('weight_norm', parse_bool),
                       ('cond_list', str), ('spk_list', str), ('sampler', str),
-                      ('batch_files', parse_bool), ('compute_dtype', str)):
+                      ('batch_files', parse_bool), ('compute_dtype', str),
+                      ('temperature', float), ('top_k', int)):
         p.add_argument('--' + name, type=typ)
     # gen.sh passes --results_path (generate.py has no such option; accepted and ignored)
     p.add_argument('--results_path', type=str)

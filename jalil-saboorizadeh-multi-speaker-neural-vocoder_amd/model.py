@@ -975,6 +975,40 @@ def top_row_bias(model, spk):
         return H.linear(emb, W_s, bias=bias)
 
 
+def sampling_controls(n_seqs, temperature=1.0, top_k=0, q_levels=256):
+    """Per-row sampling controls of Generator.__call__ as host tensors (a pure host function).
+
+    temperature and top_k are scalars (broadcast to every row) or per-row sequences, arrays or
+    tensors of length n_seqs.  temperature must be finite and >= 0 (0 = greedy, 1 = the model's
+    own softmax); top_k an integer in [0, q_levels] (0 and q_levels both mean "off").  Returns
+    None when every row is at the defaults (temperature 1, top-k off), else
+    (temperature (n_seqs,) float32, top_k (n_seqs,) int32).  Raises ValueError otherwise."""
+    def rows(v, name):
+        a = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        if a.dtype == object or a.dtype.kind not in 'biuf':
+            raise ValueError('sampling_controls: %s must be numeric' % name)
+        if a.ndim == 0:
+            a = np.broadcast_to(a, (n_seqs,))
+        if a.ndim != 1 or a.shape[0] != n_seqs:
+            raise ValueError('sampling_controls: %s has shape %s, expected a scalar or (%d,)'
+                             % (name, tuple(a.shape), n_seqs))
+        return a
+    t = rows(temperature, 'temperature').astype(np.float64)
+    if not np.all(np.isfinite(t)) or np.any(t < 0):
+        raise ValueError('sampling_controls: temperature must be finite and >= 0')
+    k = rows(top_k, 'top_k')
+    if k.dtype.kind == 'f':
+        if not np.all(np.isfinite(k)) or np.any(k != np.round(k)):
+            raise ValueError('sampling_controls: top_k must be integral')
+    k = k.astype(np.int64)
+    if np.any(k < 0) or np.any(k > q_levels):
+        raise ValueError('sampling_controls: top_k must lie in [0, %d]' % q_levels)
+    t32 = t.astype(np.float32)
+    if np.all(t32 == 1.0) and np.all((k == 0) | (k == q_levels)):
+        return None
+    return torch.from_numpy(t32.copy()), torch.from_numpy(k.astype(np.int32))
+
+
 class Generator(Runner):
     """model.py:439-520: autoregressive generation, the whole loop on the device.
 
@@ -989,6 +1023,14 @@ class Generator(Runner):
     for API compatibility; the product path always runs on the GPU.  persistent=True (the
     default) runs the sample chain between bottom-tier ticks as one persistent launch
     (gen_mlp.hip) where the shape fits, else per-sample kernels.
+
+    temperature / top_k (not in the reference; scalars or one value per row, see
+    sampling_controls) change the draw inside the same launches: over the top_k largest
+    logits of the row (ties at the k-th kept; 0 = all), argmax(z - temperature log q), and
+    plain argmax z at temperature 0 (greedy; the noise is unused).  The noise each (row, step)
+    consumes is unchanged, so a row at the defaults inside a mixed batch reproduces its
+    uncontrolled stream.  With return_logp the log-probs stay the model's own log-softmax of
+    the logits, NOT the tempered or truncated distribution that was drawn from.
     """
 
     def __init__(self, model, cuda=False):
@@ -997,10 +1039,14 @@ class Generator(Runner):
         self.last_sequences = None
 
     def __call__(self, n_seqs, seq_len, cond, spk, sampler='torch', seed=0, noise=None,
-                 return_logp=False, use_graph=True, dtype=None, persistent=True, row_offset=0):
+                 return_logp=False, use_graph=True, dtype=None, persistent=True, row_offset=0,
+                 temperature=1.0, top_k=0):
         """row_offset: these n_seqs rows are rows [row_offset, row_offset + n_seqs) of a larger
         batch (rank-sharded generation, see shard_generate): the Philox noise (sampler='philox')
-        is that of the global rows, so shards reproduce the single-process stream."""
+        is that of the global rows, so shards reproduce the single-process stream.
+        temperature, top_k: the sampling controls (class docstring); at their defaults the call
+        is the uncontrolled one, op and kernels.  return_logp's log-probs are the model's
+        log-softmax whatever the controls."""
         model = self.model
         self.reset_hidden_states()
         dev = next(model.parameters()).device
@@ -1017,6 +1063,7 @@ class Generator(Runner):
         L = model.lookback
         T = num_cond * L
         Q = model.q_levels
+        ctrl = sampling_controls(n_seqs, temperature, top_k, Q)
         weights, meta = generation_weights(model, dtype)
         row_bias = top_row_bias(model, spk)
         if noise is None and sampler == 'torch':
@@ -1025,11 +1072,15 @@ class Generator(Runner):
             noise = torch.as_tensor(noise).to(dev, torch.float32).contiguous()
             assert noise.shape == (T, n_seqs, Q), 'noise must be (T, n_seqs, Q)'
         # the registered op srnn::generate (custom_ops.py): the whole sample loop on the device
+        # (with sampling controls: srnn::generate_ctrl, the same loop with them in the draw)
         with torch.no_grad():
-            seq, logp = torch.ops.srnn.generate(
-                weights, meta, cond, row_bias, noise, int(seed) & ((1 << 63) - 1),
-                int(row_offset), (1 if use_graph else 0) | (0 if persistent else 2),
-                bool(return_logp))
+            args = (weights, meta, cond, row_bias, noise, int(seed) & ((1 << 63) - 1),
+                    int(row_offset), (1 if use_graph else 0) | (0 if persistent else 2),
+                    bool(return_logp))
+            if ctrl is None:
+                seq, logp = torch.ops.srnn.generate(*args)
+            else:
+                seq, logp = torch.ops.srnn.generate_ctrl(*args, ctrl[0].to(dev), ctrl[1].to(dev))
         assert utils.q_zero(Q) == Q // 2
         self.last_sequences = seq
         out = model.dequantize(seq[:, L:], Q).cpu()
@@ -1053,6 +1104,8 @@ def shard_generate(generator, n_seqs, cond, spk, seed, rank=None, world=None, sa
         size): the draw is then (T, noise_rows, Q), as the unpadded single-process run makes
         it, and the padding rows get unit noise (their output is discarded).
     cond: (num_cond, C) shared or (n_seqs, num_cond, C) per row; spk: int or (n_seqs,).
+    temperature / top_k (Generator's sampling controls): scalars or one value per row of the
+    whole batch; per-row values are sliced to the rank's rows like spk.
     seq_len is accepted like Generator's (the reference ignores it, model.py:455).
     Returns the host float32 (n_seqs, num_cond * lookback) batch."""
     import distributed as Dd
@@ -1068,6 +1121,10 @@ def shard_generate(generator, n_seqs, cond, spk, seed, rank=None, world=None, sa
     s = torch.as_tensor(np.asarray(spk) if not torch.is_tensor(spk) else spk).reshape(-1)
     if s.numel() > 1:
         s = s[rows]
+    ctrl = sampling_controls(n_seqs, kw.pop('temperature', 1.0), kw.pop('top_k', 0),
+                             generator.model.q_levels)
+    if ctrl is not None:
+        kw['temperature'], kw['top_k'] = ctrl[0][rows], ctrl[1][rows]
     if sampler == 'torch' and kw.get('noise') is None:
         model = generator.model
         nr = n_seqs if noise_rows is None else int(noise_rows)

@@ -95,6 +95,7 @@ _SIGS = {
     'srnn_gen_workspace_size': [_P, _I, ctypes.POINTER(_SZ)],
     'srnn_generate': [_P, _I, _I, _P, _P, _P, _U64, _P, _P, _P, _SZ, _I, _P],
     'srnn_generate2': [_P, _I, _I, _P, _P, _P, _U64, _I, _P, _P, _P, _SZ, _I, _P],
+    'srnn_generate3': [_P, _I, _I, _P, _P, _P, _U64, _I, _P, _P, _P, _SZ, _I, _P, _P, _P],
     'srnn_persistent_flag_to_f32': [_P, _P],
     'srnn_persistent_flag_or_f32': [_P, _P],
     'srnn_persistent_flag_snapshot': [_P, _P],
@@ -195,7 +196,8 @@ def lib():
 
 def exported_symbols():
     return sorted(_SIGS) + ['srnn_last_error', 'srnn_abi_version', 'srnn_gru_seq_supported',
-                            'srnn_gen_persistent_rows', 'srnn_gru_xcd_work_bytes',
+                            'srnn_gen_persistent_rows', 'srnn_gen_persistent_rows_ctrl',
+                            'srnn_gru_xcd_work_bytes',
                             'srnn_gru_xcd_bwd_work_bytes', 'srnn_gru_xcd_error',
                             'srnn_persistent_error_take', 'srnn_gemm_amax_taken',
                             'srnn_gemm_csum_taken', 'srnn_blaslt_calls', 'srnn_device_share',
@@ -375,10 +377,10 @@ def gru_xcd_bwd_work_bytes(dtype, B, D):
     return _GRU_XCD[key]
 
 
-def gen_persistent_rows(dtype, n_seqs, dim, fs0, q_levels=256):
+def gen_persistent_rows(dtype, n_seqs, dim, fs0, q_levels=256, ctrl=False):
     """Rows per group of the persistent generation loop for this shape (0: per-sample
-    kernels)."""
-    fn = lib().dll.srnn_gen_persistent_rows
+    kernels); ctrl: of a call with sampling controls (the controlled build's plan)."""
+    fn = lib().dll.srnn_gen_persistent_rows_ctrl if ctrl else lib().dll.srnn_gen_persistent_rows
     fn.argtypes = [_I, _I, _I, _I, _I]
     fn.restype = _I
     return int(fn(dcode(dtype), n_seqs, dim, fs0, q_levels))
