@@ -134,7 +134,7 @@ static int g_blaslt_calls = 0;
 // GEMMs launched through hipBLASLt so far in this process (tests: the path was taken)
 extern "C" int srnn_blaslt_calls(void) { return g_blaslt_calls; }
 
-// routing thresholds of srnn_blaslt_try: problems with fewer than min_outputs outputs or
+// routing thresholds of srnn_try_blaslt: problems with fewer than min_outputs outputs or
 // min_flop flop stay on the hand-written kernels (defaults 4 Mi, 2^33)
 extern "C" int srnn_blaslt_set_min(long long min_outputs, double min_flop) {
     routing().min_mn = min_outputs;
@@ -151,10 +151,14 @@ extern "C" int srnn_blaslt_set_tune(int n) {
 }
 
 // 0 = done, -1 = not taken (the caller runs its own kernels), > 0 = HIP / library error
-int srnn_blaslt_try(int dtype, int out_dtype, int transA, int transB, int M, int N, int K,
-                    float alpha, const void* A, int64_t lda, const void* B, int64_t ldb, float beta,
-                    void* C, int64_t ldc, const float* bias, int bias_mode, int relu,
-                    hipStream_t s, int batch, int64_t sA, int64_t sB, int64_t sC) {
+int srnn_try_blaslt(const GemmProblem& q, hipStream_t s) {
+    const int dtype = q.dtype, out_dtype = q.out_dtype, transA = q.transA, transB = q.transB;
+    const int M = q.M, N = q.N, K = q.K, batch = q.batch, bias_mode = q.bias_mode, relu = q.relu;
+    const float alpha = q.alpha, beta = q.beta;
+    const void *A = q.A, *B = q.B;
+    void* C = q.C;
+    const float* bias = q.bias;
+    const int64_t lda = q.lda, ldb = q.ldb, ldc = q.ldc, sA = q.sA, sB = q.sB, sC = q.sC;
     if (!srnn_blaslt_enabled() || dtype != SRNN_BF16 || beta != 0.f || batch < 1) return -1;
     if (batch > 1 && (bias || sA % 8 || sB % 8 || sC % 8 || sC == 0)) return -1;
     if (bias && bias_mode != 1) return -1;

@@ -256,12 +256,7 @@ static int launch_skinny_rows(const GemmArgs& g, hipStream_t s) {
     static const bool nt = env_flag("SRNN_SKINNY_NT", 0) != 0;
     auto k = nt ? skinny_kernel<T, TO, 128, BN, WM, WN, 1, NS, 2>
                 : skinny_kernel<T, TO, 128, BN, WM, WN, 1, NS>;
-    static bool attr[2] = {false, false};
-    if (!attr[nt]) {
-        SRNN_CHECK_HIP(hipFuncSetAttribute((const void*)k,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, R::LDS));
-        attr[nt] = true;
-    }
+    if (const int rc = srnn_raise_lds((const void*)k, R::LDS)) return rc;
     hipLaunchKernelGGL(k, dim3(cdiv(g.N, BN), 1), dim3(256), R::LDS, s, g);
     SRNN_LAUNCH_CHECK();
     return 0;
@@ -299,12 +294,8 @@ static int launch_t(const GemmArgs& g, int batch, hipStream_t s) {
     typedef GemmCfg<T, BM, BN, KS, WM, WN, WK> C;
     dim3 grid(cdiv(g.N, BN), cdiv(g.M, BM), batch);
     auto k = gemm_kernel<T, TO, BM, BN, KS, WM, WN, WK, KCA, KCB>;
-    static bool attr_set = false;
-    if (!attr_set && C::LDS > 65536) {
-        SRNN_CHECK_HIP(hipFuncSetAttribute((const void*)k,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS));
-    }
-    attr_set = true;
+    if (C::LDS > 65536)
+        if (const int rc = srnn_raise_lds((const void*)k, C::LDS)) return rc;
     hipLaunchKernelGGL(k, grid, dim3(256), C::LDS, s, g);
     SRNN_LAUNCH_CHECK();
     return 0;
@@ -320,33 +311,12 @@ static int launch_layout(const GemmArgs& g, int batch, int tile, hipStream_t s) 
 }
 
 template <typename T, typename TO>
-static int launch_types(const GemmArgs& g, int transA, int transB, int batch, int tile,
-                        hipStream_t s) {
-    const bool kca = !transA, kcb = transB;
+static int launch_types(const GemmArgs& g, bool kca, bool kcb, int batch, int tile, hipStream_t s) {
     if (kca && kcb) return launch_layout<T, TO, true, true>(g, batch, tile, s);
     if (kca && !kcb) return launch_layout<T, TO, true, false>(g, batch, tile, s);
     if (!kca && kcb) return launch_layout<T, TO, false, true>(g, batch, tile, s);
     return launch_layout<T, TO, false, false>(g, batch, tile, s);
 }
-
-int srnn_gemm2_try(int dtype, int out_dtype, int transA, int transB, int M, int N, int K,
-                   float alpha, const void* A, int64_t lda, const void* B, int64_t ldb,
-                   float beta, const float* Cin, int64_t ldcin, void* C, int64_t ldc,
-                   const float* bias, int bias_mode, int relu, const void* mask, int64_t ldmask,
-                   hipStream_t s);
-
-int srnn_gemm3_try(int dtype, int out_dtype, int transA, int transB, int M, int N, int K,
-                   float alpha, const void* A, int64_t lda, const void* B, int64_t ldb,
-                   float beta, const float* Cin, int64_t ldcin, void* C, int64_t ldc,
-                   const float* bias, int bias_mode, int relu, const void* mask, int64_t ldmask,
-                   int force, hipStream_t s, const unsigned short* mbi = nullptr,
-                   int64_t ldmbi = 0, unsigned short* mbo = nullptr, int64_t ldmbo = 0);
-
-int srnn_gemm_small_try(int dtype, int out_dtype, int transA, int transB, int M, int N, int K,
-                        float alpha, const void* A, int64_t lda, const void* B, int64_t ldb,
-                        float beta, const float* Cin, int64_t ldcin, void* C, int64_t ldc,
-                        const float* bias, int bias_mode, int relu, const void* mask,
-                        hipStream_t s);
 
 static bool env_on(const char* name) {
     const char* e = getenv(name);
@@ -372,13 +342,6 @@ static int pick_tile(int M, int N, int batch) {
     if (t64 >= 192) return 1;
     return 2;
 }
-
-static int gemm_core(int dtype, int out_dtype, int transA, int transB, int M, int N, int K,
-                     float alpha, const void* A, int64_t lda, int64_t strideA, const void* B,
-                     int64_t ldb, int64_t strideB, float beta, const float* Cin, int64_t ldcin,
-                     int64_t strideCin, void* C, int64_t ldc, int64_t strideC,
-                     const float* bias, int bias_mode, int relu, int batch, int tile,
-                     hipStream_t s, const void* mask, int64_t ldmask);
 
 // ---- ReLU masks as bits: bit c % 16 of the u16 of (row, column group c / 16) = (value(row,
 // c) > 0).  Two layouts (srnn_bits_index): row-major, u16 [row][c / 16] with row stride ldb;
@@ -434,148 +397,138 @@ extern "C" int srnn_relu_bits(int dtype, const void* a, int64_t lda, int M, int 
     return srnn_relu_bits_impl(dtype, a, lda, M, N, bits, ldb, (hipStream_t)stream);
 }
 
-int srnn_gemm_impl(int dtype, int out_dtype, int transA, int transB, int M, int N, int K,
-                   float alpha, const void* A, int64_t lda, int64_t strideA, const void* B,
-                   int64_t ldb, int64_t strideB, float beta, const float* Cin, int64_t ldcin,
-                   int64_t strideCin, void* C, int64_t ldc, int64_t strideC, const float* bias,
-                   int bias_mode, int relu, int batch, int tile, hipStream_t s,
-                   const void* mask, int64_t ldmask, const unsigned short* mbi, int64_t ldmbi,
-                   unsigned short* mbo, int64_t ldmbo) {
-    if (!mbi && !mbo)
-        return gemm_core(dtype, out_dtype, transA, transB, M, N, K, alpha, A, lda, strideA, B,
-                         ldb, strideB, beta, Cin, ldcin, strideCin, C, ldc, strideC, bias,
-                         bias_mode, relu, batch, tile, s, mask, ldmask);
-    SRNN_REQUIRE(batch == 1 && !(mbi && mask), "gemm: bit masks need batch 1 and no bf16 mask");
-    SRNN_REQUIRE(!(mbi && ldmbi == 0) || N % 64 == 0, "gemm: grouped mask bits need N % 64 == 0");
-    SRNN_REQUIRE(!(mbo && ldmbo == 0) || N % 64 == 0, "gemm: grouped mask bits need N % 64 == 0");
-    if (M == 0 || N == 0) return 0;
-    // the 256-tile kernel reads / writes the bits in its epilogue
-    if ((tile < 0 || tile == 5) && (tile == 5 || g_use_gemm3())) {
-        const int rc = srnn_gemm3_try(dtype, out_dtype, transA, transB, M, N, K, alpha, A, lda, B,
-                                      ldb, beta, Cin, ldcin, C, ldc, bias, bias_mode, relu, mask,
-                                      ldmask, tile == 5, s, mbi, ldmbi, mbo, ldmbo);
+
+// ---- this file's backends: the skinny NT kernel and the 128 / 64 / 32-tile general kernel
+static GemmArgs make_args(const GemmProblem& p) {
+    const int es = p.es(), eo = p.eo(), E = 16 / es;
+    GemmArgs g;
+    g.A = p.A; g.B = p.B; g.C = p.C; g.Cin = p.Cin; g.bias = p.bias;
+    g.lda = p.lda; g.ldb = p.ldb; g.ldc = p.ldc; g.ldcin = p.ldcin;
+    g.sA = p.sA; g.sB = p.sB; g.sC = p.sC; g.sCin = p.sCin;
+    g.M = p.M; g.N = p.N; g.K = p.K; g.alpha = p.alpha; g.beta = p.beta;
+    g.bias_mode = p.bias_mode; g.relu = p.relu;
+    g.mask = p.mask; g.ldmask = p.ldmask;
+    g.diag = skinny_diag();
+    // 4-column vector epilogue (skinny path): every row of C (and Cin, mask) starts on a
+    // 4-element boundary and N is whole quads
+    g.vecC = p.N % 4 == 0 && (!p.C || gemm_aligned(p.C, p.ldc, 4 * eo, 4)) &&
+             (p.beta == 0.f || !p.Cin || gemm_aligned(p.Cin, p.ldcin, 16, 4)) &&
+             (p.bias == nullptr || p.bias_mode != 1 || (uintptr_t)p.bias % 16 == 0) &&
+             (!p.mask || gemm_aligned(p.mask, p.ldmask, 4 * es, 4)) && p.batch == 1 &&
+             env_flag("SRNN_SKINNY_VEC", 1);
+    g.vecA = gemm_aligned(p.A, p.lda, 16, E) && (p.batch == 1 || p.sA % E == 0);
+    g.vecB = gemm_aligned(p.B, p.ldb, 16, E) && (p.batch == 1 || p.sB % E == 0);
+    return g;
+}
+
+// skinny NT problems (M = batch rows): small-tile deep-ring kernel.
+// Up to 512 rows: the reverse sweep's dh_0 = dgh_0 W_hh + dh_direct at 512 rows (512 x 1024
+// x 3072 with Cin) 55 -> 13.4 us against the 128-tile kernel it fell to above 256 rows
+// (tools/gemm_route_probe.py, profiles/r06_gemm_route_b512.txt)
+int srnn_try_skinny(const GemmProblem& p, hipStream_t s) {
+    const GemmArgs g = make_args(p);
+    const int KBr = 256 / p.es();
+    if (!(p.batch == 1 && !p.transA && p.transB && p.K % KBr == 0 && p.K > 0 && g.vecA &&
+          g.vecB && ((uintptr_t)p.A % 16 == 0) && ((uintptr_t)p.B % 16 == 0)))
+        return -1;
+    return gemm_dispatch_types(p.dtype, p.out_dtype, [&](auto t, auto to) {
+        return launch_skinny<decltype(t), decltype(to)>(g, s);
+    });
+}
+
+// tile 0 / 1 / 2: the 128 / 64 / 32-tile kernel (any other forced code that came this far: 32)
+int srnn_try_general(const GemmProblem& p, hipStream_t s) {
+    const GemmArgs g = make_args(p);
+    const int tile = (p.tile < 0 || p.tile == 3) ? pick_tile(p.M, p.N, p.batch) : p.tile;
+    return gemm_dispatch_types(p.dtype, p.out_dtype, [&](auto t, auto to) {
+        return launch_types<decltype(t), decltype(to)>(g, p.kca(), p.kcb(), p.batch, tile, s);
+    });
+}
+
+// ---- the router: the backends in the order they are offered a problem.  A row runs when the
+// problem's tile code forces it or leaves the choice open (tile < 0), and its guard holds;
+// a forced backend that does not take the problem is an error.  What no row takes -- and the
+// forced tiles 0 / 1 / 2 -- goes to the general kernel, which takes everything.
+struct GemmRoute {
+    int code;  // the tile code that forces this backend (-1: none)
+    bool (*guard)(const GemmProblem&, bool forced);
+    int (*run)(const GemmProblem&, hipStream_t);
+    const char* ineligible;
+};
+
+static const GemmRoute kRoutes[] = {
+    // thin problems (N <= 64 weight gradients, K <= 64 input projections)
+    {6, [](const GemmProblem& p, bool) { return p.batch == 1; }, srnn_try_thin,
+     "gemm: shape not eligible for the thin path"},
+    {4, [](const GemmProblem& p, bool forced) { return forced || (p.M <= 512 && g_use_gemm2()); },
+     srnn_try_skinny, "gemm: shape not eligible for the skinny path"},
+    // large plain bf16 problems: hipBLASLt (blaslt.cpp) unless a fused epilogue or a pending
+    // max |C| / column-sum / log-softmax request needs gemm3; strided batches too (the folded
+    // embedding . conv table, 16 x (256 x 1024 x 256) with the embedding shared: 33 us on the
+    // 128-tile kernel per step at every batch size)
+    {-1, [](const GemmProblem& p, bool) { return !p.mask && !srnn_gemm_request_pending(); },
+     srnn_try_blaslt, nullptr},
+    // large aligned bf16 problems: the 256x256 8-wave kernel (gemm3.hip)
+    {5, [](const GemmProblem& p, bool forced) { return p.batch == 1 && (forced || g_use_gemm3()); },
+     srnn_try_gemm3, "gemm: shape not eligible for the gemm3 path"},
+    // large aligned problems: the glds-ring kernel (gemm2.hip)
+    {3, [](const GemmProblem& p, bool) { return p.batch == 1 && g_use_gemm2(); }, srnn_try_gemm2,
+     "gemm: shape not eligible for the gemm2 path"},
+};
+
+static int gemm_route(const GemmProblem& p, hipStream_t s) {
+    for (const GemmRoute& r : kRoutes) {
+        const bool forced = r.code >= 0 && p.tile == r.code;
+        if (!(forced || p.tile < 0) || !r.guard(p, forced)) continue;
+        const int rc = r.run(p, s);
+        if (rc >= 0) return rc;
+        SRNN_REQUIRE(!forced, "%s", r.ineligible);
+    }
+    return srnn_try_general(p, s);
+}
+
+int srnn_gemm_run(const GemmProblem& in, hipStream_t s) {
+    GemmProblem p = in;
+    const bool bits = p.mbi || p.mbo;
+    if (bits) {
+        SRNN_REQUIRE(p.batch == 1 && !(p.mbi && p.mask), "gemm: bit masks need batch 1 and no bf16 mask");
+        SRNN_REQUIRE(!(p.mbi && p.ldmbi == 0) || p.N % 64 == 0, "gemm: grouped mask bits need N % 64 == 0");
+        SRNN_REQUIRE(!(p.mbo && p.ldmbo == 0) || p.N % 64 == 0, "gemm: grouped mask bits need N % 64 == 0");
+        if (p.M == 0 || p.N == 0) return 0;
+    }
+    SRNN_REQUIRE(p.M >= 0 && p.N >= 0 && p.K >= 0 && p.batch >= 1, "gemm: bad sizes");
+    SRNN_REQUIRE(p.dtype == SRNN_F32 || p.dtype == SRNN_BF16, "gemm: bad dtype %d", p.dtype);
+    SRNN_REQUIRE(p.out_dtype == SRNN_F32 || p.out_dtype == SRNN_BF16, "gemm: bad out dtype");
+    SRNN_REQUIRE(!(p.beta != 0.f && p.Cin == nullptr), "gemm: beta != 0 needs Cin");
+    if (p.M == 0 || p.N == 0) return 0;
+    if (!p.bias) p.bias_mode = 0;
+    if (!bits) return gemm_route(p, s);
+    // first stage for bit masks: the 256-tile kernel reads / writes the bits in its epilogue
+    if ((p.tile < 0 || p.tile == 5) && (p.tile == 5 || g_use_gemm3())) {
+        const int rc = srnn_try_gemm3(p, s);
         if (rc >= 0) return rc;
     }
     // other paths (and gemm3 without the bit epilogue, e.g. fp32 out): the bits as a mask
     // tensor in, the output's bits computed after
-    const void* mk = mask;
-    int64_t ldmk = ldmask;
-    if (mbi) {
-        const int es = dtype == SRNN_F32 ? 4 : 2;
-        void* scratch = srnn_scratch(SRNN_SCRATCH_MASK, (size_t)M * N * es);
+    GemmProblem q = p;
+    q.mbi = nullptr; q.mbo = nullptr;
+    if (p.mbi) {
+        void* scratch = srnn_scratch(SRNN_SCRATCH_MASK, (size_t)p.M * p.N * p.es());
         SRNN_REQUIRE(scratch, "gemm: mask scratch allocation failed");
-        const int64_t n = (int64_t)M * N;
-        if (dtype == SRNN_F32)
+        const int64_t n = (int64_t)p.M * p.N;
+        if (p.dtype == SRNN_F32)
             hipLaunchKernelGGL((bits_expand_kernel<float>), dim3((unsigned)cdiv(n, 256)), dim3(256),
-                               0, s, mbi, ldmbi, M, N, (float*)scratch, (int64_t)N);
+                               0, s, p.mbi, p.ldmbi, p.M, p.N, (float*)scratch, (int64_t)p.N);
         else
             hipLaunchKernelGGL((bits_expand_kernel<bf16>), dim3((unsigned)cdiv(n, 256)), dim3(256),
-                               0, s, mbi, ldmbi, M, N, (bf16*)scratch, (int64_t)N);
+                               0, s, p.mbi, p.ldmbi, p.M, p.N, (bf16*)scratch, (int64_t)p.N);
         SRNN_LAUNCH_CHECK();
-        mk = scratch;
-        ldmk = N;
+        q.mask = scratch;
+        q.ldmask = p.N;
     }
-    int rc = gemm_core(dtype, out_dtype, transA, transB, M, N, K, alpha, A, lda, strideA, B, ldb,
-                       strideB, beta, Cin, ldcin, strideCin, C, ldc, strideC, bias, bias_mode,
-                       relu, batch, tile, s, mk, ldmk);
-    if (rc || !mbo) return rc;
-    return srnn_relu_bits_impl(out_dtype, C, ldc, M, N, mbo, ldmbo, s);
-}
-
-static int gemm_core(int dtype, int out_dtype, int transA, int transB, int M, int N, int K,
-                     float alpha, const void* A, int64_t lda, int64_t strideA, const void* B,
-                     int64_t ldb, int64_t strideB, float beta, const float* Cin, int64_t ldcin,
-                     int64_t strideCin, void* C, int64_t ldc, int64_t strideC,
-                     const float* bias, int bias_mode, int relu, int batch, int tile,
-                     hipStream_t s, const void* mask, int64_t ldmask) {
-    SRNN_REQUIRE(M >= 0 && N >= 0 && K >= 0 && batch >= 1, "gemm: bad sizes");
-    SRNN_REQUIRE(dtype == SRNN_F32 || dtype == SRNN_BF16, "gemm: bad dtype %d", dtype);
-    SRNN_REQUIRE(out_dtype == SRNN_F32 || out_dtype == SRNN_BF16, "gemm: bad out dtype");
-    SRNN_REQUIRE(!(beta != 0.f && Cin == nullptr), "gemm: beta != 0 needs Cin");
-    if (M == 0 || N == 0) return 0;
-    const int es = dtype == SRNN_F32 ? 4 : 2;
-    const int E = 16 / es;
-    GemmArgs g;
-    g.A = A; g.B = B; g.C = C; g.Cin = Cin; g.bias = bias;
-    g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldcin = ldcin;
-    g.sA = strideA; g.sB = strideB; g.sC = strideC; g.sCin = strideCin;
-    g.M = M; g.N = N; g.K = K; g.alpha = alpha; g.beta = beta;
-    g.bias_mode = bias ? bias_mode : 0; g.relu = relu;
-    g.mask = mask; g.ldmask = ldmask;
-    g.diag = skinny_diag();
-    {
-        // 4-column vector epilogue (skinny path): every row of C (and Cin, mask) starts on a
-        // 4-element boundary and N is whole quads
-        const int eo = out_dtype == SRNN_F32 ? 4 : 2;
-        auto al = [](const void* p, int64_t ld, int b) {
-            return p == nullptr || (((uintptr_t)p % b == 0) && (ld % 4 == 0));
-        };
-        g.vecC = N % 4 == 0 && al(C, ldc, 4 * eo) && (beta == 0.f || al(Cin, ldcin, 16)) &&
-                 (bias == nullptr || bias_mode != 1 || (uintptr_t)bias % 16 == 0) &&
-                 al(mask, ldmask, 4 * es) && batch == 1 && env_flag("SRNN_SKINNY_VEC", 1);
-    }
-    auto aligned = [&](const void* p, int64_t ld, int64_t st) {
-        return ((uintptr_t)p % 16 == 0) && (ld % E == 0) && (batch == 1 || st % E == 0);
-    };
-    g.vecA = aligned(A, lda, strideA);
-    g.vecB = aligned(B, ldb, strideB);
-    // thin problems (N <= 64 weight gradients, K <= 64 input projections); tile 6 forces
-    if ((tile < 0 || tile == 6) && batch == 1) {
-        int rc = srnn_gemm_small_try(dtype, out_dtype, transA, transB, M, N, K, alpha, A, lda, B,
-                                     ldb, beta, Cin, ldcin, C, ldc, bias, bias_mode, relu, mask, s);
-        if (rc >= 0) return rc;
-        SRNN_REQUIRE(tile != 6, "gemm: shape not eligible for the thin path");
-    }
-    // skinny NT problems (M = batch rows): small-tile deep-ring kernel; tile 4 forces it.
-    // Up to 512 rows: the reverse sweep's dh_0 = dgh_0 W_hh + dh_direct at 512 rows (512 x 1024
-    // x 3072 with Cin) 55 -> 13.4 us against the 128-tile kernel it fell to above 256 rows
-    // (tools/gemm_route_probe.py, profiles/r06_gemm_route_b512.txt)
-    {
-        const int KBr = 256 / es;
-        const bool ok = batch == 1 && !transA && transB && K % KBr == 0 && K > 0 && g.vecA &&
-                        g.vecB && ((uintptr_t)A % 16 == 0) && ((uintptr_t)B % 16 == 0);
-        if ((tile == 4 || (tile < 0 && M <= 512 && g_use_gemm2())) && ok) {
-            if (dtype == SRNN_F32)
-                return out_dtype == SRNN_F32 ? launch_skinny<float, float>(g, s)
-                                             : launch_skinny<float, bf16>(g, s);
-            return out_dtype == SRNN_F32 ? launch_skinny<bf16, float>(g, s)
-                                         : launch_skinny<bf16, bf16>(g, s);
-        }
-        SRNN_REQUIRE(tile != 4, "gemm: shape not eligible for the skinny path");
-    }
-    // large plain bf16 problems: hipBLASLt (blaslt.cpp) unless a fused epilogue or a pending
-    // max |C| / column-sum request needs gemm3; strided batches too (the folded
-    // embedding . conv table, 16 x (256 x 1024 x 256) with the embedding shared: 33 us on the
-    // 128-tile kernel per step at every batch size)
-    if (tile < 0 && !mask && !srnn_gemm_amax_pending() && !srnn_gemm_csum_pending() &&
-        !srnn_gemm_lsm_pending()) {
-        int rc = srnn_blaslt_try(dtype, out_dtype, transA, transB, M, N, K, alpha, A, lda, B, ldb,
-                                 beta, C, ldc, bias, bias_mode, relu, s, batch, strideA, strideB,
-                                 strideC);
-        if (rc >= 0) return rc;
-    }
-    // large aligned bf16 problems: the 256x256 8-wave kernel (gemm3.hip); tile 5 forces it
-    if ((tile < 0 || tile == 5) && batch == 1 && (tile == 5 || g_use_gemm3())) {
-        int rc = srnn_gemm3_try(dtype, out_dtype, transA, transB, M, N, K, alpha, A, lda, B, ldb,
-                                beta, Cin, ldcin, C, ldc, bias, bias_mode, relu, mask, ldmask,
-                                tile == 5, s);
-        if (rc >= 0) return rc;
-        SRNN_REQUIRE(tile != 5, "gemm: shape not eligible for the gemm3 path");
-    }
-    // large aligned problems: the glds-ring kernel (gemm2.hip); tile 3 forces it
-    if ((tile < 0 || tile == 3) && batch == 1 && g_use_gemm2()) {
-        int rc = srnn_gemm2_try(dtype, out_dtype, transA, transB, M, N, K, alpha, A, lda, B, ldb,
-                                beta, Cin, ldcin, C, ldc, bias, bias_mode, relu, mask, ldmask, s);
-        if (rc >= 0) return rc;
-        SRNN_REQUIRE(tile != 3, "gemm: shape not eligible for the gemm2 path");
-    }
-    if (tile < 0 || tile == 3) tile = pick_tile(M, N, batch);
-    if (dtype == SRNN_F32) {
-        if (out_dtype == SRNN_F32) return launch_types<float, float>(g, transA, transB, batch, tile, s);
-        return launch_types<float, bf16>(g, transA, transB, batch, tile, s);
-    }
-    if (out_dtype == SRNN_F32) return launch_types<bf16, float>(g, transA, transB, batch, tile, s);
-    return launch_types<bf16, bf16>(g, transA, transB, batch, tile, s);
+    const int rc = gemm_route(q, s);
+    if (rc || !p.mbo) return rc;
+    return srnn_relu_bits_impl(p.out_dtype, p.C, p.ldc, p.M, p.N, p.mbo, p.ldmbo, s);
 }
 
 extern "C" int srnn_gemm_bits(int dtype, int out_dtype, int transA, int transB, int M, int N,
@@ -584,9 +537,13 @@ extern "C" int srnn_gemm_bits(int dtype, int out_dtype, int transA, int transB, 
                               int64_t ldc, const float* bias, int bias_mode, int relu, int tile,
                               const unsigned short* mask_bits, int64_t ldmb,
                               unsigned short* bits_out, int64_t ldbo, void* stream) {
-    return srnn_gemm_impl(dtype, out_dtype, transA, transB, M, N, K, alpha, A, lda, 0, B, ldb, 0,
-                          beta, Cin, ldcin, 0, C, ldc, 0, bias, bias_mode, relu, 1, tile,
-                          (hipStream_t)stream, nullptr, 0, mask_bits, ldmb, bits_out, ldbo);
+    GemmProblem p;
+    p.dtype = dtype; p.out_dtype = out_dtype; p.transA = transA; p.transB = transB;
+    p.M = M; p.N = N; p.K = K; p.alpha = alpha; p.beta = beta;
+    p.A = A; p.lda = lda; p.B = B; p.ldb = ldb; p.C = C; p.ldc = ldc;
+    p.Cin = Cin; p.ldcin = ldcin; p.bias = bias; p.bias_mode = bias_mode; p.relu = relu;
+    p.mbi = mask_bits; p.ldmbi = ldmb; p.mbo = bits_out; p.ldmbo = ldbo; p.tile = tile;
+    return srnn_gemm_run(p, (hipStream_t)stream);
 }
 
 extern "C" int srnn_gemm(int dtype, int out_dtype, int transA, int transB, int M, int N, int K,
@@ -595,7 +552,12 @@ extern "C" int srnn_gemm(int dtype, int out_dtype, int transA, int transB, int M
                          int64_t strideCin, void* C, int64_t ldc, int64_t strideC,
                          const float* bias, int bias_mode, int relu, int batch, int tile,
                          const void* mask, int64_t ldmask, void* stream) {
-    return srnn_gemm_impl(dtype, out_dtype, transA, transB, M, N, K, alpha, A, lda, strideA, B,
-                          ldb, strideB, beta, Cin, ldcin, strideCin, C, ldc, strideC, bias,
-                          bias_mode, relu, batch, tile, (hipStream_t)stream, mask, ldmask);
+    GemmProblem p;
+    p.dtype = dtype; p.out_dtype = out_dtype; p.transA = transA; p.transB = transB;
+    p.M = M; p.N = N; p.K = K; p.batch = batch; p.alpha = alpha; p.beta = beta;
+    p.A = A; p.lda = lda; p.sA = strideA; p.B = B; p.ldb = ldb; p.sB = strideB;
+    p.C = C; p.ldc = ldc; p.sC = strideC; p.Cin = Cin; p.ldcin = ldcin; p.sCin = strideCin;
+    p.bias = bias; p.bias_mode = bias_mode; p.relu = relu;
+    p.mask = mask; p.ldmask = ldmask; p.tile = tile;
+    return srnn_gemm_run(p, (hipStream_t)stream);
 }

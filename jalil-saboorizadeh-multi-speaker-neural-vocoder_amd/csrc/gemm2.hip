@@ -218,13 +218,7 @@ template <typename T, typename TO, bool KCA, bool KCB>
 static int launch2(const Gemm2Args& g, hipStream_t s) {
     typedef G2<T> C;
     auto k = gemm2_kernel<T, TO, KCA, KCB>;
-    static bool attr = false;
-    if (!attr) {
-        SRNN_CHECK_HIP(hipFuncSetAttribute((const void*)k,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           C::NS * C::SLOT));
-        attr = true;
-    }
+    if (const int rc = srnn_raise_lds((const void*)k, C::NS * C::SLOT)) return rc;
     dim3 grid((g.M / 128) * (g.N / 128), 1, g.ksplit);
     hipLaunchKernelGGL(k, grid, dim3(256), C::NS * C::SLOT, s, g);
     SRNN_LAUNCH_CHECK();
@@ -239,29 +233,23 @@ static int launch2_layout(const Gemm2Args& g, bool kca, bool kcb, hipStream_t s)
     return launch2<T, TO, false, false>(g, s);
 }
 
-// Returns -1 if the shape/layout is not eligible (caller falls back to the general
-// kernel), else the launch status.
-int srnn_gemm2_try(int dtype, int out_dtype, int transA, int transB, int M, int N, int K,
-                   float alpha, const void* A, int64_t lda, const void* B, int64_t ldb,
-                   float beta, const float* Cin, int64_t ldcin, void* C, int64_t ldc,
-                   const float* bias, int bias_mode, int relu, const void* mask, int64_t ldmask,
-                   hipStream_t s) {
-    const int es = dtype == SRNN_F32 ? 4 : 2;
+// Returns -1 if the shape/layout is not eligible (the router goes on to the general kernel),
+// else the launch status.
+int srnn_try_gemm2(const GemmProblem& p, hipStream_t s) {
+    const int es = p.es();
     const int KB = 128 / es;
+    const int M = p.M, N = p.N, K = p.K;
     if (M % 128 || N % 128 || K % KB || K == 0) return -1;
-    auto al = [&](const void* p, int64_t ld) {
-        return ((uintptr_t)p % 16 == 0) && ((ld * es) % 16 == 0);
-    };
-    if (!al(A, lda) || !al(B, ldb)) return -1;
+    if (!gemm_aligned(p.A, p.lda, 16, 16 / es) || !gemm_aligned(p.B, p.ldb, 16, 16 / es)) return -1;
     Gemm2Args g;
-    g.A = A; g.B = B; g.C = C; g.Cin = Cin; g.bias = bias; g.mask = mask;
-    g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldcin = ldcin; g.ldmask = ldmask;
-    g.M = M; g.N = N; g.K = K; g.alpha = alpha; g.beta = beta;
-    g.bias_mode = bias ? bias_mode : 0; g.relu = relu;
+    g.A = p.A; g.B = p.B; g.C = p.C; g.Cin = p.Cin; g.bias = p.bias; g.mask = p.mask;
+    g.lda = p.lda; g.ldb = p.ldb; g.ldc = p.ldc; g.ldcin = p.ldcin; g.ldmask = p.ldmask;
+    g.M = M; g.N = N; g.K = K; g.alpha = p.alpha; g.beta = p.beta;
+    g.bias_mode = p.bias_mode; g.relu = p.relu;
     // split K when the tile grid cannot fill the chip (wgrad shapes: K = B*T rows)
     const int tiles = (M / 128) * (N / 128);
     int ks = 1;
-    const bool plain = beta == 0.f && !bias && !relu && !mask && out_dtype == SRNN_F32;
+    const bool plain = p.beta == 0.f && !p.bias && !p.relu && !p.mask && p.out_dtype == SRNN_F32;
     if (plain) {
         while (tiles * ks < 512 && (K / (ks * 2)) % KB == 0 && K / (ks * 2) >= 8 * KB) ks *= 2;
     }
@@ -269,28 +257,22 @@ int srnn_gemm2_try(int dtype, int out_dtype, int transA, int transB, int M, int 
     g.part = nullptr;
     // split K deterministically (partials + ordered sum, as gemm3) where C allows the float4
     // sum; fp32 atomics otherwise (SRNN_G3_SPLITK_PART=0 forces them)
-    const bool det = ks > 1 && env_flag("SRNN_G3_SPLITK_PART", 1) && ldc % 4 == 0 &&
-                     (uintptr_t)C % 16 == 0;
+    const bool det = ks > 1 && env_flag("SRNN_G3_SPLITK_PART", 1) && p.ldc % 4 == 0 &&
+                     (uintptr_t)p.C % 16 == 0;
     if (det) {
         g.part = srnn_splitk_scratch((size_t)ks * M * N * sizeof(float));
         SRNN_REQUIRE(g.part, "gemm2: split-K scratch allocation failed");
-        const int rc = dtype == SRNN_F32 ? launch2_layout<float, float>(g, !transA, transB, s)
-                                         : launch2_layout<bf16, float>(g, !transA, transB, s);
-        if (rc) return rc;
-        return srnn_splitk_sum(g.part, (float*)C, ldc, M, N, ks, s);
-    }
-    if (ks > 1) {
-        if (ldc == N) {
-            SRNN_CHECK_HIP(hipMemsetAsync(C, 0, (size_t)M * N * 4, s));
+    } else if (ks > 1) {
+        if (p.ldc == N) {
+            SRNN_CHECK_HIP(hipMemsetAsync(p.C, 0, (size_t)M * N * 4, s));
         } else {
-            SRNN_CHECK_HIP(hipMemset2DAsync(C, ldc * 4, 0, (size_t)N * 4, M, s));
+            SRNN_CHECK_HIP(hipMemset2DAsync(p.C, p.ldc * 4, 0, (size_t)N * 4, M, s));
         }
     }
-    const bool kca = !transA, kcb = transB;
-    if (dtype == SRNN_F32) {
-        if (out_dtype == SRNN_F32) return launch2_layout<float, float>(g, kca, kcb, s);
-        return launch2_layout<float, bf16>(g, kca, kcb, s);
-    }
-    if (out_dtype == SRNN_F32) return launch2_layout<bf16, float>(g, kca, kcb, s);
-    return launch2_layout<bf16, bf16>(g, kca, kcb, s);
+    // (ks > 1 only for fp32 outputs)
+    const int rc = gemm_dispatch_types(p.dtype, p.out_dtype, [&](auto t, auto to) {
+        return launch2_layout<decltype(t), decltype(to)>(g, p.kca(), p.kcb(), s);
+    });
+    if (rc || !det) return rc;
+    return srnn_splitk_sum(g.part, (float*)p.C, p.ldc, M, N, ks, s);
 }

@@ -97,11 +97,11 @@ __device__ __forceinline__ void g3_epilogue_t(const Gemm3Args& g, floatx4 (&acc)
     // stores would also wait for every older store and in-flight DMA piece (vmcnt is in
     // order), serialising 32 round trips per tile.  Exactly 32 stores per wave follow.
     TO* Cp = reinterpret_cast<TO*>(g.C);
-    // (MB == 2 kernels take no bf16 mask: srnn_gemm3_try admits grouped bits without one)
+    // (MB == 2 kernels take no bf16 mask: srnn_try_gemm3 admits grouped bits without one)
     const bf16* mask = MB == 2 ? nullptr : reinterpret_cast<const bf16*>(g.mask);
     const int rbase = m0 + wm * 128 + (lane & 15);
     const int cbase = n0 + wn * 64 + (lane >> 4) * 4;
-    // MB == 2 (the da1 GEMM's kernels) is lean: no bias, ReLU or blocked copy (srnn_gemm3_try
+    // MB == 2 (the da1 GEMM's kernels) is lean: no bias, ReLU or blocked copy (srnn_try_gemm3
     // routes such calls elsewhere), so none of their code or registers is in the epilogue; the
     // (the same for the column-sum kernels measured slower: da2 0.67 -> 0.70 ms, not kept)
     constexpr bool LEAN = MB == 2;
@@ -925,181 +925,17 @@ __global__ __launch_bounds__(512, 1) void gemm3p_kernel(Gemm3Args g) {
 }
 
 // ---------------------------------------------------------------------------------
-// 8-phase ping-pong kernel for NT products (both operands k-contiguous: the MLP layers'
-// forward and input-gradient GEMMs, the upsampling and GRU input projections' forward).
-// The pair-mode LDS layout (two 64 KiB slots of 64-deep k-tiles, 128-B rows, XOR-swizzled
-// 16-B slots) with the two wave groups X = waves 0-3 (output rows 0-127 of the tile) and
-// Y = waves 4-7 (rows 128-255) one segment apart: every k-tile is 8 segments per group,
-//      R0 | M0 | R1 | M1 | R2 | M2 | R3 | M3       (Y one segment behind X)
-// Rp: the LDS reads of phase p (R0: the m-fragments 0-3 and n-fragments 0-1 of both 32-k
-//     units, 12 ds_read_b128; R1: m 4-7, n 2-3), completed (lgkmcnt(0)) inside the
-//     segment; R2 / R3 issue the A / B pieces of k-tile t + 2 into the slot k-tile t was
-//     just read from (4 global_load_lds per wave each); R3 also waits (counted vmcnt) for
-//     k-tile t + 1, whose reads start two segments later in both groups;
-// Mp: one quadrant of the wave's 128 x 64 outputs (4 m x 2 n fragments x both k units =
-//     16 v_mfma_f32_16x16x32_bf16).
-// Every segment ends with a raw s_barrier, so while one group's waves wait on LDS reads or
-// issue DMA, the other group's wave on the same SIMD runs its MFMAs.  A k-tile's DMA has
-// ten segments (five phases) between its issue and the wait that needs it; the epilogue of
-// a finished tile runs in the next k-tile's R0, its stores counted in R3's vmcnt.
-// ---------------------------------------------------------------------------------
-// Ping-pong mode: the pair-mode LDS layout (64-deep stages, 2 x 64 KiB slots) with the
-// two waves of each SIMD working in opposite phases.  Waves 0-3 (X) and 4-7 (Y) each
-// alternate a LOAD segment (12 fragment reads of one 32-deep k-unit into registers) and
-// a COMPUTE segment (its 32 MFMAs of that unit), Y one segment behind X, so while one
-// wave of a SIMD keeps the matrix pipe busy its partner fetches its next operands:
+// Ping-pong over the 32-deep ring: the two waves of each SIMD work in opposite phases.
+// Waves 0-3 (X) and 4-7 (Y) each alternate a LOAD segment (the 12 fragment reads of one
+// 32-deep stage into registers) and a COMPUTE segment (its 32 MFMAs), Y one segment behind X,
+// so while one wave of a SIMD keeps the matrix pipe busy its partner fetches its next operands:
 //      X:  L0 | C0 | L1 | C1 | L2 | ...
 //      Y:  -- | L0 | C0 | L1 | C1 | ...
-// with one raw s_barrier between segments.  X alone streams HBM -> LDS: in its LOAD
-// segment of a stage's first unit it issues all 16 DMA pieces (of 64) of the next stage
-// into the slot Y finished reading one segment earlier, and waits for them at the end of
-// its COMPUTE segment of the stage's second unit, three segments later.  A finished tile's
-// epilogue runs in the wave's next LOAD segment.
-template <typename TO, bool KCA, bool KCB, bool SW>
-__global__ __launch_bounds__(512, 1) void gemm3pp_kernel(Gemm3Args g) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int wm = wave & 1, wn = wave >> 1;
-    const int grp = wave >> 2, wx = wave & 3;
-    const int ntm = g.M / g3::BM, ntn = g.N / g3::BN;
-    const int ntiles = ntm * ntn;
-    const int nunits = ntiles * g.ksplit;
-    const int G = gridDim.x;
-    const int nmine = (nunits - (int)blockIdx.x + G - 1) / G;
-    const int kslice = g.K / g.ksplit;
-    const int nk = kslice / g3p::BK;
-    const int S = nmine * nk;
-    const bf16* A = reinterpret_cast<const bf16*>(g.A);
-    const bf16* B = reinterpret_cast<const bf16*>(g.B);
-
-    auto unit = [&](int i, int& m0, int& n0, int& kbeg) {
-        const int v = (int)blockIdx.x + i * G;
-        const int z = v / ntiles;
-        const int t = g3_xcd_remap(v - z * ntiles, ntiles);
-        m0 = (t / ntn) * g3::BM;
-        n0 = (t % ntn) * g3::BN;
-        kbeg = z * kslice;
-    };
-
-    floatx4 acc[8][4];
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
-
-    // X wave wx streams pieces c = 4 i + wx (i = 0..7) of each operand: pieces i and
-    // i + 2 share the source swizzle and sit 8 pieces (64 rows / 16 k-rows) apart
-    const int64_t stepA = KCA ? (int64_t)64 * g.lda : (int64_t)16 * g.lda;
-    const int64_t stepB = KCB ? (int64_t)64 * g.ldb : (int64_t)16 * g.ldb;
-    int iu = 0, kti = 0;
-    const bf16* srcA[2];
-    const bf16* srcB[2];
-    auto set_src = [&]() {
-        int m0, n0, kb;
-        unit(iu, m0, n0, kb);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int c = 4 * i + wx;
-            srcA[i] = g3p_src<KCA>(A, g.lda, m0, kb, c, lane);
-            srcB[i] = g3p_src<KCB>(B, g.ldb, n0, kb, c, lane);
-        }
-    };
-    auto koffA = [&](int kt) { return KCA ? (int64_t)kt * g3p::BK : (int64_t)kt * g3p::BK * g.lda; };
-    auto koffB = [&](int kt) { return KCB ? (int64_t)kt * g3p::BK : (int64_t)kt * g3p::BK * g.ldb; };
-    auto issue_stage = [&](char* img) {      // X waves only: 8 + 8 pieces of the next stage
-        const int64_t oa = koffA(kti), ob = koffB(kti);
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-            __builtin_amdgcn_global_load_lds(G3_GLB(srcA[i & 1] + oa + (i >> 1) * stepA),
-                                             G3_LDS(img + (4 * i + wx) * 1024), 16, 0, 0);
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-            __builtin_amdgcn_global_load_lds(G3_GLB(srcB[i & 1] + ob + (i >> 1) * stepB),
-                                             G3_LDS(img + g3p::OPB + (4 * i + wx) * 1024), 16,
-                                             0, 0);
-        if (++kti == nk) {
-            kti = 0;
-            ++iu;
-            if (iu < nmine) set_src();
-        }
-    };
-    if (grp == 0) set_src();
-
-    bf16x8 a[8], b[4];
-    auto bar = []() {
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    // prologue: stage 0 resident before anyone reads
-    if (S > 0 && grp == 0) {
-        issue_stage(smem);
-        g3_wait_vm<0>();
-    }
-    bar();
-    if (grp == 1) bar();                     // Y runs one segment behind
-    int ic = 0, ktc = 0;
-    bool epi = false;
-    const int U = 2 * S;
-    for (int u = 0; u < U; ++u) {
-        const int st = u >> 1, h = u & 1;
-        const char* img = smem + (st & 1) * g3p::SLOT;
-        // ---- LOAD segment
-        if (epi) {
-            int m0, n0, kb;
-            unit(ic - 1, m0, n0, kb);
-            if (!(g.diag & 8)) g3_epilogue<TO, SW>(g, acc, m0, n0, wm, wn, lane, kb);
-            epi = false;
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) b[j] = g3p_frag<KCB>(img + g3p::OPB, wn * 64 + j * 16, h, lane);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) a[i] = g3p_frag<KCA>(img, wm * 128 + i * 16, h, lane);
-        if (grp == 0 && h == 0 && st + 1 < S && !(g.diag & 4))
-            issue_stage(smem + ((st + 1) & 1) * g3p::SLOT);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        bar();
-        // ---- COMPUTE segment
-        __builtin_amdgcn_s_setprio(1);
-        if (!(g.diag & 1)) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    acc[i][j] = SW ? __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[j], a[i], acc[i][j], 0, 0, 0)
-                                   : __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
-        } else {
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j][0] += (float)a[i][0] * (float)b[j][0];
-        }
-        __builtin_amdgcn_s_setprio(0);
-        if (h == 1) {
-            if (++ktc == nk) {
-                ktc = 0;
-                ++ic;
-                epi = true;
-            }
-            // X: the next stage's DMA (issued three segments ago) lands before Y and X read it
-            if (grp == 0 && !(g.diag & 2)) g3_wait_vm<0>();
-        }
-        bar();
-    }
-    if (grp == 0) bar();
-    if (epi) {
-        int m0, n0, kb;
-        unit(ic - 1, m0, n0, kb);
-        g3_epilogue<TO, SW>(g, acc, m0, n0, wm, wn, lane, kb);
-    }
-}
-
-// ---------------------------------------------------------------------------------
-// Ping-pong over the 32-deep ring (mode 4): the LOAD / COMPUTE alternation of the
-// ping-pong kernel on the 5-slot ring of 32-deep stages, so the DMA can be spread: every
+// with one raw s_barrier between segments.  On the 5-slot ring the DMA is spread: every
 // wave issues its 4 pieces of stage u + NS - 1 in its LOAD segment of unit u (into the
 // slot Y finished reading one segment earlier), and waits, counted, for stage v at the end
-// of the segment before X reads it (X: its COMPUTE of v - 1; Y: its LOAD of v - 1).
+// of the segment before X reads it (X: its COMPUTE of v - 1; Y: its LOAD of v - 1).  A finished
+// tile's epilogue runs in the wave's next LOAD segment.
 template <typename TO, bool KCA, bool KCB, bool SW>
 __global__ __launch_bounds__(512, 1) void gemm3q_kernel(Gemm3Args g) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1247,14 +1083,6 @@ __global__ __launch_bounds__(512, 1) void gemm3q_kernel(Gemm3Args g) {
     }
 }
 
-static int g3_mode() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("SRNN_G3MODE");
-        v = e ? atoi(e) : 2;
-    }
-    return v;
-}
 
 static int g3_ncu() {
     static int ncu = 0;
@@ -1266,89 +1094,150 @@ static int g3_ncu() {
     return ncu;
 }
 
-// The 8-phase ping-pong NT kernel (gemm3e.hip) for plain / bias / ReLU / bits-out epilogues
-// of NT products with K a multiple of 64, K >= 128 (SRNN_G3E=0: the pair-mode kernel)
-static bool g3e_on() { return env_flag("SRNN_G3E", 0) != 0; }
+// One-shot epilogue requests (srnn_gemm_amax_next / _amax_blk_next / _csum_next /
+// _logsoftmax_next).  A request waits for the next gemm3 launch whose kernel variant computes
+// it and is taken there, in launch3, beside the choice of that variant -- so "taken" and "the
+// launched kernel does it" cannot disagree; its *_taken call reports that and clears it.
+struct G3Requests {
+    unsigned* amax = nullptr;  // max |C| of a bf16-output product
+    bf16* blk = nullptr;       // (with amax) also the column-blocked copy of the output
+    float* csum = nullptr;     // column sums of a bf16-output product
+    int lsm = 0;               // row log-softmax of an fp32-output NT product with N = 256
+    int amax_taken = 0, csum_taken = 0, lsm_taken = 0;
+};
+static G3Requests g3_req;
+
+int srnn_gemm_request_pending() { return g3_req.amax || g3_req.csum || g3_req.lsm; }
+
+extern "C" int srnn_gemm_amax_next(unsigned* amax) {
+    g3_req.amax = amax;
+    g3_req.blk = nullptr;
+    g3_req.amax_taken = 0;
+    return 0;
+}
+
+extern "C" int srnn_gemm_amax_blk_next(unsigned* amax, void* blk) {
+    g3_req.amax = amax;
+    g3_req.blk = (bf16*)blk;
+    g3_req.amax_taken = 0;
+    return 0;
+}
+
+extern "C" int srnn_gemm_csum_next(float* part) {
+    g3_req.csum = part;
+    g3_req.csum_taken = 0;
+    return 0;
+}
+
+extern "C" int srnn_gemm_logsoftmax_next(void) {
+    g3_req.lsm = 1;
+    g3_req.lsm_taken = 0;
+    return 0;
+}
+
+extern "C" int srnn_gemm_logsoftmax_taken(void) {
+    const int t = g3_req.lsm_taken;
+    g3_req.lsm = 0;
+    g3_req.lsm_taken = 0;
+    return t;
+}
+
+extern "C" int srnn_gemm_csum_taken(void) {
+    const int t = g3_req.csum_taken;
+    g3_req.csum = nullptr;
+    g3_req.csum_taken = 0;
+    return t;
+}
+
+extern "C" int srnn_gemm_amax_taken(void) {
+    const int t = g3_req.amax_taken;
+    g3_req.amax = nullptr;
+    g3_req.blk = nullptr;
+    g3_req.amax_taken = 0;
+    return t;
+}
 
 template <typename TO, bool KCA, bool KCB, bool SW>
-static int launch3(const Gemm3Args& g, hipStream_t s) {
-    if constexpr (KCA && KCB && SW) {
-        if (g3e_on()) {
-            const int rc = srnn_gemm3e_launch(g, sizeof(TO) == 4, g3_ncu(), s);
-            if (rc >= 0) return rc;
-        }
-    }
-    // mode 0: 32-deep 5-slot ring; 1: 64-deep pair mode; 2 (default): pair mode when an
-    // operand is k-contiguous (full-line DMA pieces), the ring otherwise
-    const int mode = g3_mode();
-    const bool k64 = (g.K / g.ksplit) % g3p::BK == 0;
-    const bool pp = mode == 3 && k64;
-    // mode 2 also takes the ring ping-pong for the NN shapes with enough tiles for two rounds
-    // (A k-contiguous, B n-contiguous, plain output): measured on the step's upsampling
+static int launch3(Gemm3Args g, hipStream_t s) {
+    constexpr bool BF = sizeof(TO) == 2;
+    // pair mode (64-deep stages) when an operand is k-contiguous (full-line DMA pieces) and
+    // the k-slice is whole 64-deep stages, the 32-deep 5-slot ring otherwise
+    const bool pairable = (KCA || KCB) && (g.K / g.ksplit) % g3p::BK == 0;
+    const bool grouped = g.mbi && g.ldmbi == 0;
+    // the pending requests this launch serves: all need a pair-mode kernel's vector epilogue.
+    // max |C|: no Cin, no row-major bit masks; column sums: the plain bf16 epilogue only (no
+    // Cin, bit masks or max |C|; M % 128 == 0 holds here); log-softmax: one tile column of an
+    // NT product, column bias at most, no ReLU
+    const bool amax = BF && SW && g3_req.amax && pairable && g.beta == 0.f &&
+                      (!g.mbi || grouped) && !g.mbo;
+    const bool csum = BF && SW && g3_req.csum && !amax && pairable && g.beta == 0.f && !g.mbi &&
+                      !g.mbo;
+    const bool lsm = !BF && SW && KCA && KCB && g3_req.lsm && pairable && g.N == g3::BN &&
+                     g.ksplit == 1 && g.beta == 0.f && !g.mask && !g.mbi && !g.mbo &&
+                     (!g.bias || g.bias_mode == 1) && !g.relu;
+    // the ring ping-pong for the NN shapes with enough tiles for two rounds (A k-contiguous,
+    // B n-contiguous, plain output): measured on the step's upsampling
     // dX (32768 x 1024 x 16384: 1090 -> 900 us) and GRU dX (32768 x 1024 x 3072: 247 -> 204 us);
     // at one round of tiles (8192 x 1024 x 3072 / 4096) the pair mode stays ahead
     // (profiles/r04_gemm_modes_b512.txt)
     const int units = (g.M / g3::BM) * (g.N / g3::BN) * g.ksplit;
-    const bool q = !g.csp && (mode == 4 ||
-                   (mode == 2 && KCA && !KCB && g.ksplit == 1 && !g.mbi && !g.mbo && !g.amax &&
-                    !g.mask && units >= 2 * g3_ncu() && env_flag("SRNN_G3_NNQ", 1)));
-    const bool pair = !pp && !q && (mode == 1 || (mode == 2 && (KCA || KCB))) && k64;
+    const bool q = !csum && KCA && !KCB && g.ksplit == 1 && !g.mbi && !g.mbo && !amax && !g.mask &&
+                   units >= 2 * g3_ncu() && env_flag("SRNN_G3_NNQ", 1);
+    const bool pair = !q && pairable;
     // unit-1 fragment prefetch (gemm3p PF): measured 14 % faster on the bf16 NT shapes (MLP
     // hidden forward, upsampling forward, B = 512), 3 % on NN; slower on the fp32-output NT
     // logits GEMM (N = 256), which keeps the plain schedule.  SRNN_G3_PF=0/1 overrides.
     const int pfe = env_flag("SRNN_G3_PF", -1);
     const bool pf = pfe >= 0 ? pfe != 0 : !(sizeof(TO) == 4 && KCA && KCB);
     auto k = q ? gemm3q_kernel<TO, KCA, KCB, SW>
-               : pp ? gemm3pp_kernel<TO, KCA, KCB, SW>
-                    : pair ? (pf ? gemm3p_kernel<TO, KCA, KCB, SW, false, true>
-                                 : gemm3p_kernel<TO, KCA, KCB, SW>)
-                           : gemm3_kernel<TO, KCA, KCB, SW>;
-    int ki = q ? 3 : pp ? 2 : pair ? (pf ? 8 : 1) : 0;
-    const bool grouped = g.mbi && g.ldmbi == 0;
-    SRNN_REQUIRE(!grouped || (sizeof(TO) == 2 && SW && pair && !g.mbo &&
-                              g.K / g.ksplit >= 2 * g3p::BK),
+               : pair ? (pf ? gemm3p_kernel<TO, KCA, KCB, SW, false, true>
+                            : gemm3p_kernel<TO, KCA, KCB, SW>)
+                      : gemm3_kernel<TO, KCA, KCB, SW>;
+    SRNN_REQUIRE(!grouped || (BF && SW && pair && !g.mbo && g.K / g.ksplit >= 2 * g3p::BK),
                  "gemm3: grouped mask bits need the bf16 pair-mode kernel and >= 2 k-chunks");
-    if constexpr (sizeof(TO) == 2 && SW) {
+    // the blocked copy needs whole 4-column blocks (N % 256 == 0 holds here); the grouped-bits
+    // kernels write none (the caller sees taken == 1 and reads the row-major da1)
+    auto take_amax = [&](bool with_blk) {
+        g.amax = g3_req.amax;
+        g.blk = with_blk ? g3_req.blk : nullptr;
+        g3_req.amax = nullptr;
+        g3_req.blk = nullptr;
+        g3_req.amax_taken = g.blk ? 2 : 1;
+    };
+    if constexpr (BF && SW) {
         if (grouped) {               // grouped bits staged by LDS-DMA (+ max |C| for the dTab)
             // with the unit-1 fragment prefetch (SRNN_G3_BITS_PF=0: without): da1 1.11 -> 1.09
             // ms at B = 512 on one box (profiles/r05_da1_grouped_bits.txt)
             const bool bpf = env_flag("SRNN_G3_BITS_PF", 1) != 0;
-            k = g.amax ? (bpf ? gemm3p_kernel<TO, KCA, KCB, SW, 2, true, true>
-                              : gemm3p_kernel<TO, KCA, KCB, SW, 2, false, true>)
-                       : gemm3p_kernel<TO, KCA, KCB, SW, 2>;
-            ki = g.amax ? (bpf ? 15 : 14) : 13;
-        } else if (g.mbi || g.mbo) { // ReLU bit masks (srnn_gemm3_try admits modes 0-2 only)
+            k = amax ? (bpf ? gemm3p_kernel<TO, KCA, KCB, SW, 2, true, true>
+                            : gemm3p_kernel<TO, KCA, KCB, SW, 2, false, true>)
+                     : gemm3p_kernel<TO, KCA, KCB, SW, 2>;
+            if (amax) take_amax(false);
+        } else if (g.mbi || g.mbo) { // row-major ReLU bit masks
             k = pair ? gemm3p_kernel<TO, KCA, KCB, SW, true> : gemm3_kernel<TO, KCA, KCB, SW, true>;
-            ki += 4;
-        } else if (g.csp && pair) {   // column sums wanted (srnn_gemm_csum_next)
+        } else if (csum) {            // column sums wanted (srnn_gemm_csum_next)
             k = pf ? gemm3p_kernel<TO, KCA, KCB, SW, 0, true, false, 1>
                    : gemm3p_kernel<TO, KCA, KCB, SW, 0, false, false, 1>;
-            ki = pf ? 12 : 11;
-        } else if (g.amax && pair) {  // max |C| wanted (srnn_gemm_amax_next)
+            g.csp = g3_req.csum;
+            g3_req.csum = nullptr;
+            g3_req.csum_taken = 1;
+        } else if (amax) {            // max |C| wanted (srnn_gemm_amax_next)
             // (SRNN_G3_AMX_PF: with the unit-1 fragment prefetch as well)
-            const int amx_pf = env_flag("SRNN_G3_AMX_PF", 0);
-            k = amx_pf ? gemm3p_kernel<TO, KCA, KCB, SW, false, true, true>
-                       : gemm3p_kernel<TO, KCA, KCB, SW, false, false, true>;
-            ki = amx_pf ? 10 : 9;
+            k = env_flag("SRNN_G3_AMX_PF", 0) ? gemm3p_kernel<TO, KCA, KCB, SW, false, true, true>
+                                              : gemm3p_kernel<TO, KCA, KCB, SW, false, false, true>;
+            take_amax(true);
         }
     }
-    if constexpr (sizeof(TO) == 4 && SW && KCA && KCB) {
-        if (g.lsm) {                 // row log-softmax in the epilogue (srnn_gemm_logsoftmax_next)
-            SRNN_REQUIRE(pair && g.N == g3::BN && g.ksplit == 1,
-                         "gemm3: the log-softmax epilogue needs one pair-mode tile column");
+    if constexpr (!BF && SW && KCA && KCB) {
+        if (lsm) {                   // row log-softmax in the epilogue (srnn_gemm_logsoftmax_next)
             k = gemm3p_kernel<TO, KCA, KCB, SW, 0, false, false, 0, 1>;
-            ki = 16;
+            g.lsm = 1;
+            g3_req.lsm = 0;
+            g3_req.lsm_taken = 1;
         }
     }
-    SRNN_REQUIRE(!g.csp || pair, "gemm3: column sums need the pair-mode kernel");
-    const int lds = (pp || pair) ? g3p::LDS + (grouped ? 16 * 1024 : g.lsm ? 8 * 1024 : 0)
-                                 : g3::LDS;
-    static bool attr[24] = {};
-    if (!attr[ki]) {
-        SRNN_CHECK_HIP(hipFuncSetAttribute((const void*)k,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        attr[ki] = true;
-    }
+    const int lds = pair ? g3p::LDS + (grouped ? 16 * 1024 : g.lsm ? 8 * 1024 : 0) : g3::LDS;
+    if (const int rc = srnn_raise_lds((const void*)k, lds)) return rc;
     const int ncu = g3_ncu();
     dim3 grid(units < ncu ? units : ncu);
     hipLaunchKernelGGL(k, grid, dim3(g3::NT), lds, s, g);
@@ -1381,141 +1270,35 @@ static int g3_pick_split(int tiles, int K) {
     return best;
 }
 
-// Returns -1 if the shape/layout is not eligible (caller falls back), else the status.
-// force: take the path whenever eligible (tile == 5), else only when the 256-tile grid
+// Returns -1 if the shape/layout is not eligible (the router goes on), else the status.
+// tile == 5 (forced): take the path whenever eligible, else only when the 256-tile grid
 // (with split-K) occupies the chip at least as well as the 128-tile kernel would.
-// max |C| request for the next bf16-output GEMM that takes the gemm3 path (srnn_gemm_amax_next)
-static unsigned*& g3_amax_pending() {
-    static unsigned* p = nullptr;
-    return p;
-}
-static int& g3_amax_taken() {
-    static int t = 0;
-    return t;
-}
-static bf16*& g3_blk_pending() {
-    static bf16* p = nullptr;
-    return p;
-}
-
-int srnn_gemm_amax_pending() { return g3_amax_pending() != nullptr; }
-
-extern "C" int srnn_gemm_amax_next(unsigned* amax) {
-    g3_amax_pending() = amax;
-    g3_blk_pending() = nullptr;
-    g3_amax_taken() = 0;
-    return 0;
-}
-
-extern "C" int srnn_gemm_amax_blk_next(unsigned* amax, void* blk) {
-    g3_amax_pending() = amax;
-    g3_blk_pending() = (bf16*)blk;
-    g3_amax_taken() = 0;
-    return 0;
-}
-
-// column-sum request for the next bf16-output GEMM that takes the gemm3 pair path
-static float*& g3_csum_pending() {
-    static float* p = nullptr;
-    return p;
-}
-static int& g3_csum_taken() {
-    static int t = 0;
-    return t;
-}
-
-int srnn_gemm_csum_pending() { return g3_csum_pending() != nullptr; }
-
-extern "C" int srnn_gemm_csum_next(float* part) {
-    g3_csum_pending() = part;
-    g3_csum_taken() = 0;
-    return 0;
-}
-
-// log-softmax request for the next fp32-output NT GEMM with N = 256 that takes the gemm3
-// pair path (the SampleLevelMLP's logits)
-static int& g3_lsm_pending() {
-    static int p = 0;
-    return p;
-}
-static int& g3_lsm_taken() {
-    static int t = 0;
-    return t;
-}
-
-int srnn_gemm_lsm_pending() { return g3_lsm_pending(); }
-
-extern "C" int srnn_gemm_logsoftmax_next(void) {
-    g3_lsm_pending() = 1;
-    g3_lsm_taken() = 0;
-    return 0;
-}
-
-extern "C" int srnn_gemm_logsoftmax_taken(void) {
-    const int t = g3_lsm_taken();
-    g3_lsm_pending() = 0;
-    g3_lsm_taken() = 0;
-    return t;
-}
-
-extern "C" int srnn_gemm_csum_taken(void) {
-    const int t = g3_csum_taken();
-    g3_csum_pending() = nullptr;
-    g3_csum_taken() = 0;
-    return t;
-}
-
-extern "C" int srnn_gemm_amax_taken(void) {
-    const int t = g3_amax_taken();
-    g3_amax_pending() = nullptr;
-    g3_blk_pending() = nullptr;
-    g3_amax_taken() = 0;
-    return t;
-}
-
-int srnn_gemm3_try(int dtype, int out_dtype, int transA, int transB, int M, int N, int K,
-                   float alpha, const void* A, int64_t lda, const void* B, int64_t ldb,
-                   float beta, const float* Cin, int64_t ldcin, void* C, int64_t ldc,
-                   const float* bias, int bias_mode, int relu, const void* mask, int64_t ldmask,
-                   int force, hipStream_t s, const unsigned short* mbi, int64_t ldmbi,
-                   unsigned short* mbo, int64_t ldmbo) {
-    if (dtype != SRNN_BF16) return -1;
-    if ((mbi || mbo) && (out_dtype != SRNN_BF16 || g3_mode() > 2)) return -1;
-    if ((mbi && ((uintptr_t)mbi % 8 || ldmbi % 4 || mask)) ||
-        (mbo && ((uintptr_t)mbo % 8 || ldmbo % 4 || ldmbo == 0 || beta != 0.f)))
+int srnn_try_gemm3(const GemmProblem& p, hipStream_t s) {
+    const int M = p.M, N = p.N, K = p.K;
+    const bool force = p.tile == 5;
+    if (p.dtype != SRNN_BF16) return -1;
+    if ((p.mbi || p.mbo) && p.out_dtype != SRNN_BF16) return -1;
+    if ((p.mbi && ((uintptr_t)p.mbi % 8 || p.ldmbi % 4 || p.mask)) ||
+        (p.mbo && ((uintptr_t)p.mbo % 8 || p.ldmbo % 4 || p.ldmbo == 0 || p.beta != 0.f)))
         return -1;
     // grouped bits in (ldmbi = 0): the pair-mode kernels only (an operand k-contiguous, K a
-    // multiple of 64, modes 1-2); the caller's fallback expands them otherwise.  K >= 128:
+    // multiple of 64); the router's fallback expands them otherwise.  K >= 128:
     // the kernel stages tile iu's bits into buffer iu & 1 while issuing the previous tile's
     // LAST k-chunk, and with one chunk per tile (K = 64) that is the stage whose epilogue
     // still reads tile iu - 2's bits from the same buffer
-    if (mbi && ldmbi == 0 &&
-        (!(g3_mode() == 1 || (g3_mode() == 2 && (!transA || transB))) || K % g3p::BK ||
-         K < 2 * g3p::BK || mbo || (uintptr_t)mbi % 16 || bias || relu || beta != 0.f))
+    if (p.mbi && p.ldmbi == 0 &&
+        (!(p.kca() || p.kcb()) || K % g3p::BK || K < 2 * g3p::BK || p.mbo ||
+         (uintptr_t)p.mbi % 16 || p.bias || p.relu || p.beta != 0.f))
         return -1;
     if (M % g3::BM || N % g3::BN || K % g3::BK || K == 0) return -1;
-    auto al = [](const void* p, int64_t ld, int es) {
-        return ((uintptr_t)p % 16 == 0) && ((ld * es) % 16 == 0);
-    };
-    if (!al(A, lda, 2) || !al(B, ldb, 2)) return -1;
-    if ((uintptr_t)C % (out_dtype == SRNN_F32 ? 16 : 8) || ldc % 4) return -1;
-    if (beta != 0.f && (!Cin || (uintptr_t)Cin % 16 || ldcin % 4)) return -1;
-    if (mask && ((uintptr_t)mask % 8 || ldmask % 4)) return -1;
-    if (bias && bias_mode == 1 && (uintptr_t)bias % 16) return -1;
-    Gemm3Args g;
-    g.A = A; g.B = B; g.C = C; g.Cin = Cin; g.bias = bias; g.mask = mask;
-    g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldcin = ldcin; g.ldmask = ldmask;
-    g.M = M; g.N = N; g.K = K; g.alpha = alpha; g.beta = beta;
-    g.bias_mode = bias ? bias_mode : 0; g.relu = relu;
-    g.diag = env_flag("SRNN_G3DIAG", 0);
-    g.mbi = mbi; g.ldmbi = ldmbi; g.mbo = mbo; g.ldmbo = ldmbo;
-    g.amax = nullptr;
-    g.blk = nullptr;
-    g.csp = nullptr;
-    g.lsm = 0;
+    if (!gemm_aligned(p.A, p.lda, 16, 8) || !gemm_aligned(p.B, p.ldb, 16, 8)) return -1;
+    if (!gemm_aligned(p.C, p.ldc, p.out_dtype == SRNN_F32 ? 16 : 8, 4)) return -1;
+    if (p.beta != 0.f && (!p.Cin || !gemm_aligned(p.Cin, p.ldcin, 16, 4))) return -1;
+    if (p.mask && !gemm_aligned(p.mask, p.ldmask, 8, 4)) return -1;
+    if (p.bias && p.bias_mode == 1 && (uintptr_t)p.bias % 16) return -1;
     const int tiles = (M / g3::BM) * (N / g3::BN);
-    const bool plain = beta == 0.f && !bias && !relu && !mask && !mbi && !mbo &&
-                       out_dtype == SRNN_F32;
+    const bool plain = p.beta == 0.f && !p.bias && !p.relu && !p.mask && !p.mbi && !p.mbo &&
+                       p.out_dtype == SRNN_F32;
     const int ks = plain ? g3_pick_split(tiles, K) : 1;
     if (!force) {
         const int64_t wg3 = (int64_t)tiles * ks;
@@ -1524,56 +1307,32 @@ int srnn_gemm3_try(int dtype, int out_dtype, int transA, int transB, int M, int 
         //  top-tier NT projections, 2048 x 3072/4096 x 1024; 32 tiles do not)
         if (wg3 < 96 && wg2 > wg3) return -1;
     }
+    Gemm3Args g;
+    g.A = p.A; g.B = p.B; g.C = p.C; g.Cin = p.Cin; g.bias = p.bias; g.mask = p.mask;
+    g.lda = p.lda; g.ldb = p.ldb; g.ldc = p.ldc; g.ldcin = p.ldcin; g.ldmask = p.ldmask;
+    g.M = M; g.N = N; g.K = K; g.alpha = p.alpha; g.beta = p.beta;
+    g.bias_mode = p.bias_mode; g.relu = p.relu;
+    g.diag = env_flag("SRNN_G3DIAG", 0);
+    g.mbi = p.mbi; g.ldmbi = p.ldmbi; g.mbo = p.mbo; g.ldmbo = p.ldmbo;
+    g.amax = nullptr;            // the requests: launch3
+    g.blk = nullptr;
+    g.csp = nullptr;
+    g.lsm = 0;
     g.ksplit = ks;
     g.part = nullptr;
-    const bool det = ks > 1 && env_flag("SRNN_G3_SPLITK_PART", 1) && g3_mode() <= 2 &&
-                     ldc % 4 == 0 && (uintptr_t)C % 16 == 0;
-    if (ks > 1 && det) {
+    if (ks == 1)
+        return p.out_dtype == SRNN_F32 ? launch3_layout<float, true>(g, p.kca(), p.kcb(), s)
+                                       : launch3_layout<bf16, true>(g, p.kca(), p.kcb(), s);
+    if (env_flag("SRNN_G3_SPLITK_PART", 1) && gemm_aligned(p.C, p.ldc, 16, 4)) {
         // partial tiles in a grow-only scratch, then one ordered sum (no memset, no atomics)
         g.part = srnn_splitk_scratch((size_t)ks * M * N * sizeof(float));
         SRNN_REQUIRE(g.part, "gemm3: split-K scratch allocation failed");
-    } else if (ks > 1) {
-        if (ldc == N) {
-            SRNN_CHECK_HIP(hipMemsetAsync(C, 0, (size_t)M * N * 4, s));
-        } else {
-            SRNN_CHECK_HIP(hipMemset2DAsync(C, ldc * 4, 0, (size_t)N * 4, M, s));
-        }
+    } else if (p.ldc == N) {
+        SRNN_CHECK_HIP(hipMemsetAsync(p.C, 0, (size_t)M * N * 4, s));
+    } else {
+        SRNN_CHECK_HIP(hipMemset2DAsync(p.C, p.ldc * 4, 0, (size_t)N * 4, M, s));
     }
-    const bool kca = !transA, kcb = transB;
-    if (ks > 1) {
-        const int rc = launch3_layout<float, false>(g, kca, kcb, s);
-        if (rc || !g.part) return rc;
-        return srnn_splitk_sum((const float*)g.part, (float*)C, ldc, M, N, ks, s);
-    }
-    if (out_dtype == SRNN_F32) {
-        if (g3_lsm_pending() && N == g3::BN && g.ksplit == 1 && beta == 0.f && !mask && !mbi && !mbo &&
-            (!bias || bias_mode == 1) && kca && kcb && K % g3p::BK == 0 &&
-            (g3_mode() == 1 || g3_mode() == 2)) {
-            g.lsm = 1;
-            g3_lsm_pending() = 0;
-            g3_lsm_taken() = 1;
-        }
-        return launch3_layout<float, true>(g, kca, kcb, s);
-    }
-    // max |C| (srnn_gemm_amax_next): computed by the pair-mode kernels (an operand
-    // k-contiguous, K a multiple of 64, no bit masks) -- the request is taken only then
-    if (g3_amax_pending() && beta == 0.f && (!mbi || ldmbi == 0) && !mbo && (kca || kcb) &&
-        K % g3p::BK == 0 && g3_mode() <= 2 && (g3_mode() != 0)) {
-        g.amax = g3_amax_pending();
-        // the blocked copy needs whole 4-column blocks (N % 256 == 0 holds here); the grouped-
-        // bits kernels write none (the caller sees taken == 1 and reads the row-major da1)
-        g.blk = (mbi && ldmbi == 0) ? nullptr : g3_blk_pending();
-        g3_amax_pending() = nullptr;
-        g3_blk_pending() = nullptr;
-        g3_amax_taken() = g.blk ? 2 : 1;
-    }
-    // column sums (srnn_gemm_csum_next): the pair-mode kernels' plain bf16 epilogue only
-    // (no Cin, bit masks or max |C|); M % 128 == 0 holds here
-    if (g3_csum_pending() && !g.amax && beta == 0.f && !mbi && !mbo && (kca || kcb) &&
-        K % g3p::BK == 0 && (g3_mode() == 1 || g3_mode() == 2)) {
-        g.csp = g3_csum_pending();
-        g3_csum_pending() = nullptr;
-        g3_csum_taken() = 1;
-    }
-    return launch3_layout<bf16, true>(g, kca, kcb, s);
+    const int rc = launch3_layout<float, false>(g, p.kca(), p.kcb(), s);
+    if (rc || !g.part) return rc;
+    return srnn_splitk_sum((const float*)g.part, (float*)p.C, p.ldc, M, N, ks, s);
 }

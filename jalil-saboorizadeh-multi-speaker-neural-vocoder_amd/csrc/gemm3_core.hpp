@@ -1,4 +1,4 @@
-// Shared pieces of the 256 x 256 bf16 GEMM kernels (gemm3.hip, gemm3e.hip): the argument
+// Shared pieces of the 256 x 256 bf16 GEMM kernels (gemm3.hip): the argument
 // block, the LDS image layouts (ring mode: 32-deep stages; pair mode: 64-deep stages of 128-B
 // rows) and their per-lane DMA sources / fragment reads, the XCD-aware tile order.
 #pragma once
@@ -167,6 +167,3 @@ __device__ __forceinline__ bf16x8 g3p_frag(const char* img, int f0, int u, int l
     }
 }
 
-
-// gemm3e.hip: the 8-phase ping-pong NT kernel; returns -1 if the call is not eligible
-int srnn_gemm3e_launch(const Gemm3Args& g, bool out_f32, int ncu, hipStream_t s);

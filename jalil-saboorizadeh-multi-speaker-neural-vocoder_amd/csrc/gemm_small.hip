@@ -441,43 +441,40 @@ static int launch_small_k(const void* A, int64_t lda, const void* B, int64_t ldb
 }
 
 // Returns -1 when the problem is not one of the two thin shapes.
-int srnn_gemm_small_try(int dtype, int out_dtype, int transA, int transB, int M, int N, int K,
-                        float alpha, const void* A, int64_t lda, const void* B, int64_t ldb,
-                        float beta, const float* Cin, int64_t ldcin, void* C, int64_t ldc,
-                        const float* bias, int bias_mode, int relu, const void* mask,
-                        hipStream_t s) {
-    if (mask) return -1;
+int srnn_try_thin(const GemmProblem& p, hipStream_t s) {
+    const int M = p.M, N = p.N, K = p.K;
+    const void *A = p.A, *B = p.B;
+    const int64_t lda = p.lda, ldb = p.ldb, ldc = p.ldc;
+    if (p.mask) return -1;
     // small N: plain fp32 output, B (K x N)
-    if (N <= 64 && !transB && beta == 0.f && !bias && !relu && out_dtype == SRNN_F32 &&
+    if (N <= 64 && !p.transB && p.beta == 0.f && !p.bias && !p.relu && p.out_dtype == SRNN_F32 &&
         K >= 128 && (int64_t)M * K >= (1 << 16)) {
+        float* C = (float*)p.C;
         // vector path: 4 adjacent m per lane (aligned rows of A)
-        const int es = dtype == SRNN_F32 ? 4 : 2;
-        if (transA && M % 4 == 0 && lda % 4 == 0 && ((uintptr_t)A % (4 * es)) == 0 &&
+        if (p.transA && M % 4 == 0 && gemm_aligned(A, lda, 4 * p.es(), 4) &&
             env_flag("SRNN_SMALL_NT", 1))
-            return dtype == SRNN_F32
-                       ? launch_small_nt<float>(A, lda, B, ldb, (float*)C, ldc, M, N, K, alpha, s)
-                       : launch_small_nt<bf16>(A, lda, B, ldb, (float*)C, ldc, M, N, K, alpha, s);
-        if (dtype == SRNN_F32)
-            return transA ? launch_small_n<float, true>(A, lda, B, ldb, (float*)C, ldc, M, N, K, alpha, s)
-                          : launch_small_n<float, false>(A, lda, B, ldb, (float*)C, ldc, M, N, K, alpha, s);
-        return transA ? launch_small_n<bf16, true>(A, lda, B, ldb, (float*)C, ldc, M, N, K, alpha, s)
-                      : launch_small_n<bf16, false>(A, lda, B, ldb, (float*)C, ldc, M, N, K, alpha, s);
+            return p.dtype == SRNN_F32
+                       ? launch_small_nt<float>(A, lda, B, ldb, C, ldc, M, N, K, p.alpha, s)
+                       : launch_small_nt<bf16>(A, lda, B, ldb, C, ldc, M, N, K, p.alpha, s);
+        if (p.dtype == SRNN_F32)
+            return p.transA ? launch_small_n<float, true>(A, lda, B, ldb, C, ldc, M, N, K, p.alpha, s)
+                            : launch_small_n<float, false>(A, lda, B, ldb, C, ldc, M, N, K, p.alpha, s);
+        return p.transA ? launch_small_n<bf16, true>(A, lda, B, ldb, C, ldc, M, N, K, p.alpha, s)
+                        : launch_small_n<bf16, false>(A, lda, B, ldb, C, ldc, M, N, K, p.alpha, s);
     }
     // small K: NT with the full epilogue (column bias only).  K = 64 without Cin over enough
     // rows for gemm3's own occupancy rule (>= 96 tiles of 256 x 256) goes to gemm3 instead
     // (the top tier's 64-sample input projection at 512 rows, 8192 x 1024 x 64 with bias, fp32
     // out: 42 -> 15 us, profiles/r06_gemm_route_b512.txt); SRNN_SMALLK_G3=0 keeps it here
-    const bool to_g3 = K == 64 && beta == 0.f && M % 256 == 0 && N % 256 == 0 &&
-                       (int64_t)(M / 256) * (N / 256) >= 96 && dtype == SRNN_BF16 &&
+    const bool to_g3 = K == 64 && p.beta == 0.f && M % 256 == 0 && N % 256 == 0 &&
+                       (int64_t)(M / 256) * (N / 256) >= 96 && p.dtype == SRNN_BF16 &&
                        env_flag("SRNN_SMALLK_G3", 1);
-    if (K <= 64 && K > 0 && !transA && transB && (!bias || bias_mode == 1) && M >= 256 && !to_g3) {
-        if (dtype == SRNN_F32)
-            return out_dtype == SRNN_F32
-                       ? launch_small_k<float, float>(A, lda, B, ldb, C, ldc, Cin, ldcin, bias, M, N, K, alpha, beta, relu, s)
-                       : launch_small_k<float, bf16>(A, lda, B, ldb, C, ldc, Cin, ldcin, bias, M, N, K, alpha, beta, relu, s);
-        return out_dtype == SRNN_F32
-                   ? launch_small_k<bf16, float>(A, lda, B, ldb, C, ldc, Cin, ldcin, bias, M, N, K, alpha, beta, relu, s)
-                   : launch_small_k<bf16, bf16>(A, lda, B, ldb, C, ldc, Cin, ldcin, bias, M, N, K, alpha, beta, relu, s);
-    }
+    if (K <= 64 && K > 0 && !p.transA && p.transB && (!p.bias || p.bias_mode == 1) && M >= 256 &&
+        !to_g3)
+        return gemm_dispatch_types(p.dtype, p.out_dtype, [&](auto t, auto to) {
+            return launch_small_k<decltype(t), decltype(to)>(A, lda, B, ldb, p.C, ldc, p.Cin,
+                                                             p.ldcin, p.bias, M, N, K, p.alpha,
+                                                             p.beta, p.relu, s);
+        });
     return -1;
 }

@@ -580,15 +580,10 @@ int tier_tick(Ctx& c, int k, int off, int par) {
         const size_t tlds = (size_t)(TI_OB + TI_RB) * (t.in_dim | 1) * sizeof(float);
         if (tlds <= 160 * 1024) {
             // (attribute raised once, to the whole LDS, before the first launch that needs it)
-            static bool attr[2] = {false, false};
-            const int ai = dt == SRNN_F32 ? 0 : 1;
-            if (tlds > 65536 && !attr[ai]) {
-                SRNN_CHECK_HIP(hipFuncSetAttribute(
-                    dt == SRNN_F32 ? (const void*)tier_input_tiled_kernel<float>
-                                   : (const void*)tier_input_tiled_kernel<bf16>,
-                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                attr[ai] = true;
-            }
+            if (tlds > 65536)
+                RET(srnn_raise_lds(dt == SRNN_F32 ? (const void*)tier_input_tiled_kernel<float>
+                                                  : (const void*)tier_input_tiled_kernel<bf16>,
+                                   160 * 1024));
             NoiseJob nz{c.noise, c.seed, c.row0, 0, nullptr};
             int planes = 1;
             if (k == (c.b.fold ? 1 : 0) && c.pl && c.b.lq && env_flag("SRNN_GEN_NOISE_AHEAD", 1)) {
@@ -903,9 +898,15 @@ extern "C" int srnn_generate3(const SrnnModel* m, int n_seqs, int n_cond, const 
                 break;
             }
             // Wfold[j] = W_ih0 (3D x D) . W_up1[j] (D x D, rows j D .. j D + D - 1), bf16 out
-            rc = srnn_gemm_impl(m->dtype, m->dtype, 0, 0, 3 * D, D, D, 1.f, t0.w_ih[0], D, 0,
-                                t1.w_up, D, (int64_t)D * D, 0.f, nullptr, 0, 0, c.b.wfold, D,
-                                (int64_t)3 * D * D, nullptr, 0, 0, t1.frame_size, -1, s);
+            {
+                GemmProblem p;
+                p.dtype = p.out_dtype = m->dtype;
+                p.M = 3 * D; p.N = D; p.K = D; p.batch = t1.frame_size;
+                p.A = t0.w_ih[0]; p.lda = D;
+                p.B = t1.w_up; p.ldb = D; p.sB = (int64_t)D * D;
+                p.C = c.b.wfold; p.ldc = D; p.sC = (int64_t)3 * D * D;
+                rc = srnn_gemm_run(p, s);
+            }
             if (rc) break;
             // [W_hh1; b_hh1] after the folded rows, and gh1 of the first upper tick
             const size_t g0 = (size_t)t1.frame_size * 3 * D;
@@ -941,10 +942,15 @@ extern "C" int srnn_generate3(const SrnnModel* m, int n_seqs, int n_cond, const 
                 // Min1 = W_ih1 (3D x D) . W_in1 (D x in_dim), zero-padded to TA_AP columns;
                 // P1 = bf16(row_bias) . W_ih1^T + b_ih1
                 rc = hipMemsetAsync(c.b.min1, 0, (size_t)3 * D * TA_AP * es, s) ? 2 : 0;
-                if (!rc)
-                    rc = srnn_gemm_impl(m->dtype, m->dtype, 0, 0, 3 * D, t1.in_dim, D, 1.f,
-                                        t1.w_ih[0], D, 0, t1.w_in, t1.in_dim, 0, 0.f, nullptr, 0,
-                                        0, c.b.min1, TA_AP, 0, nullptr, 0, 0, 1, -1, s);
+                if (!rc) {
+                    GemmProblem p;
+                    p.dtype = p.out_dtype = m->dtype;
+                    p.M = 3 * D; p.N = t1.in_dim; p.K = D;
+                    p.A = t1.w_ih[0]; p.lda = D;
+                    p.B = t1.w_in; p.ldb = t1.in_dim;
+                    p.C = c.b.min1; p.ldc = TA_AP;
+                    rc = srnn_gemm_run(p, s);
+                }
                 if (!rc) {
                     if (m->dtype == SRNN_F32)
                         hipLaunchKernelGGL((copy_cast_kernel<float>), dim3(cdiv(B * D, 256)),

@@ -11,6 +11,7 @@
 //     verdict: all ranks skip the update together and raise together;
 //   * srnn_persistent_error_take (host, synchronises) reports and clears it.
 #include "samplernn_hip_internal.hpp"
+#include <unordered_set>
 
 namespace {
 constexpr int MAXDEV = 64;
@@ -195,5 +196,13 @@ extern "C" int srnn_persistent_flag_or(const void* src, int dtype, void* stream)
     hipLaunchKernelGGL(flag_or_bf16_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, f,
                        (const bf16*)src);
     SRNN_LAUNCH_CHECK();
+    return 0;
+}
+
+int srnn_raise_lds(const void* kernel, int bytes) {
+    static std::unordered_set<const void*> raised;
+    if (raised.count(kernel)) return 0;
+    SRNN_CHECK_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    raised.insert(kernel);
     return 0;
 }

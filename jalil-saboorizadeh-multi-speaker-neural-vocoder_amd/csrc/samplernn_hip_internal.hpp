@@ -1,15 +1,7 @@
 // Internal (C++) entry points shared between translation units of the library.
 #pragma once
-#include "common.hpp"
+#include "gemm_problem.hpp"
 
-int srnn_gemm_impl(int dtype, int out_dtype, int transA, int transB, int M, int N, int K,
-                   float alpha, const void* A, int64_t lda, int64_t strideA, const void* B,
-                   int64_t ldb, int64_t strideB, float beta, const float* Cin, int64_t ldcin,
-                   int64_t strideCin, void* C, int64_t ldc, int64_t strideC, const float* bias,
-                   int bias_mode, int relu, int batch, int tile, hipStream_t s,
-                   const void* mask = nullptr, int64_t ldmask = 0,
-                   const unsigned short* mbi = nullptr, int64_t ldmbi = 0,
-                   unsigned short* mbo = nullptr, int64_t ldmbo = 0);
 int srnn_relu_bits_impl(int dtype, const void* a, int64_t lda, int M, int N, unsigned short* bits,
                         int64_t ldb, hipStream_t s);
 
@@ -24,9 +16,16 @@ static inline int linear_fwd(int dt, int odt, int M, int N, int K, const void* x
                              const void* W, int64_t ldw, const float* bias, void* y, int64_t ldy,
                              int relu, hipStream_t s, float beta = 0.f, const float* yin = nullptr,
                              int64_t ldyin = 0) {
-    return srnn_gemm_impl(dt, odt, 0, 1, M, N, K, 1.f, x, ldx, 0, W, ldw, 0, beta, yin, ldyin, 0,
-                          y, ldy, 0, bias, 1, relu, 1, -1, s);
+    GemmProblem p;
+    p.dtype = dt; p.out_dtype = odt; p.transB = 1;
+    p.M = M; p.N = N; p.K = K; p.beta = beta;
+    p.A = x; p.lda = ldx; p.B = W; p.ldb = ldw; p.C = y; p.ldc = ldy;
+    p.Cin = yin; p.ldcin = ldyin; p.bias = bias; p.bias_mode = 1; p.relu = relu;
+    return srnn_gemm_run(p, s);
 }
+
+// raises a kernel's dynamic LDS limit to `bytes`, once per kernel in the process (persist.hip)
+int srnn_raise_lds(const void* kernel, int bytes);
 
 // integer value of an environment switch (dflt when unset or empty)
 static inline int env_flag(const char* name, int dflt) {
@@ -64,14 +63,5 @@ int srnn_splitk_sum(const float* part, float* C, int64_t ldc, int M, int N, int 
 // blaslt.cpp: plain large bf16 GEMMs (alpha, optional per-column bias, optional ReLU, beta 0)
 // through hipBLASLt; 0 done, -1 not taken (run the library's own kernels), > 0 error
 int srnn_blaslt_enabled();
-// (batch > 1: strided batches, element strides sA / sB / sC; sA or sB may be 0 -- one
-//  operand shared by every batch)
-int srnn_blaslt_try(int dtype, int out_dtype, int transA, int transB, int M, int N, int K,
-                    float alpha, const void* A, int64_t lda, const void* B, int64_t ldb, float beta,
-                    void* C, int64_t ldc, const float* bias, int bias_mode, int relu,
-                    hipStream_t s, int batch = 1, int64_t sA = 0, int64_t sB = 0, int64_t sC = 0);
-// gemm3.hip: a max |C| request (srnn_gemm_amax_next) waits for the next bf16 gemm3 launch
-int srnn_gemm_amax_pending();
-// gemm3.hip: a column-sum request (srnn_gemm_csum_next) waits for the next bf16 gemm3 launch
-int srnn_gemm_csum_pending();
-int srnn_gemm_lsm_pending();
+// (srnn_try_blaslt, gemm_problem.hpp; batch > 1: strided batches, element strides sA / sB /
+//  sC; sA or sB may be 0 -- one operand shared by every batch)
