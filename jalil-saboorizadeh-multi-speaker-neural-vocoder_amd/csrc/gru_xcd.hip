@@ -50,10 +50,15 @@ __device__ __forceinline__ void gx_note_failure(const int* err, int* sticky) {
 
 // Row layout of a sweep (host-chosen, gx_layout): G groups x MT tiles of RV <= 16 valid rows;
 // tile m of group g holds batch rows [(g MT + m) RV, +RV).  MT > 1 (B > 16 G: several
-// 128-row sets per launch) runs the tiles of one step back to back in every workgroup, so
-// one tile's hand-off latency hides behind the others' work; RV < 16 (B < 128) keeps all
-// eight XCDs busy with fewer rows each.  Hand-off slots are indexed per tile with a 16-row
-// stride whatever RV is.
+// 128-row sets per launch) runs the tiles of one step back to back in every workgroup.  Only
+// the wait for a tile's hand-off to be published hides behind the other tiles' work; each
+// tile still pays its own serial phases (hand-off read, MFMA chain, barrier, reduction and
+// gate math, stores), so an MT-tile step costs about MT one-tile steps.  The reverse sweep
+// takes the tiles two at a time through the phases after the MFMAs (BT = 2 below); the
+// forward sweep measured no faster that way (its time is the hand-off reads themselves,
+// DESIGN section 3) and keeps one tile per phase.  RV < 16 (B < 128) keeps all eight XCDs
+// busy with fewer rows each.  Hand-off slots are indexed per tile with a 16-row stride
+// whatever RV is.
 struct GruXArgs {
     const float* gi; int64_t ldgi; int64_t sgi;     // gi[b][t] (3D, includes b_ih)
     const float* h0;                                // (B, D) fp32
@@ -617,7 +622,10 @@ __global__ __launch_bounds__(gx::NTHR, 2) void gru_xcd_bwd_kernel(GruXBwdArgs a)
 // the gates (the granule's bytes ARE the MFMA A operand, unpacked nowhere) and slot 3, the
 // tag, meets zero weights (tags are small positive integers: finite bf16 bit patterns, so
 // tag x 0 = 0).  The W_hh^T fragments are gathered into that order once, in the prologue.
-template <int UPW, int MT>
+// BT: tiles per batch.  1: every (step, tile) runs its phases on its own; 2 (the default at
+// MT > 1; SRNN_GX_BATCH=0 takes BT = 1): the two tiles of a batch share each phase after the
+// MFMAs -- see the batched form below
+template <int UPW, int MT, int BT = 1>
 __global__ __launch_bounds__(gx::NTHR, 2) void gru_xcd_bwd_pk_kernel(GruXBwdArgs a) {
     using namespace gx;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -626,8 +634,8 @@ __global__ __launch_bounds__(gx::NTHR, 2) void gru_xcd_bwd_pk_kernel(GruXBwdArgs
     const int B = a.B, RV = a.RV;
     constexpr int KW = NW;                                      // NU' = D / 8 = UPW * NW
     constexpr int NTB = 2;
-    float* red = (float*)smem;                                  // [2][KW][NTB][4][PS]
-    const size_t red_bytes = (size_t)2 * KW * NTB * 4 * PS * sizeof(float);
+    float* red = (float*)smem;                                  // [2][BT][KW][NTB][4][PS]
+    const size_t red_bytes = (size_t)2 * BT * KW * NTB * 4 * PS * sizeof(float);
     int* gsh = (int*)(smem + red_bytes);
     const int g = blockIdx.x % a.G, p = blockIdx.x / a.G;
     if (tid == 0) hx_group_arrive(a.census + g * a.P + p);
@@ -732,6 +740,155 @@ __global__ __launch_bounds__(gx::NTHR, 2) void gru_xcd_bwd_pk_kernel(GruXBwdArgs
     if (MT > 1)
         for (int k = 0; k < 5 * MT; ++k) sl[k * NTHR + tid] = 0.f;
     fetch(a.Fr - 1, 0, dyv, gr, gz, gn, gg, hp);
+    if constexpr (BT == 2) {
+    // ---- batched form: tiles (m0, m0 + 1) of a step share the barrier, the reduction reads,
+    // the gate backward, the publish, the operand fetch and the output stores.  The register
+    // file is full (W_hh^T slice + one poll buffer), so the two polls stay one after the other
+    // through the same x[UPW]; red holds both tiles' partials, double-buffered by the batch
+    // parity (one barrier per batch, as the per-tile form's per tile).
+    static_assert(MT % 2 == 0, "gru_xcd_bwd_pk: a batch is two tiles");
+    float dy1, gr1, gz1, gn1, gg1, hp1;
+    fetch(a.Fr - 1, 1, dy1, gr1, gz1, gn1, gg1, hp1);
+    // tile m's hand-off -> MFMAs -> partial sums into red[par][k]
+    auto poll_mma = [&](int t, int m, int par, int k) {
+        floatx4 acc[NTB];
+#pragma unroll
+        for (int i = 0; i < NTB; ++i) acc[i] = floatx4{0.f, 0.f, 0.f, 0.f};
+        const uint32_t tag = (uint32_t)(a.Fr - 1 - t);              // dgh_{t+1}
+        const uint32_t base = (uint32_t)((((size_t)((t + 1) & 1)) * bufw +
+                                          (size_t)(g * MT + m) * RG * D) * 8);
+        uint4 x[UPW];
+        int spins = 0;
+        uint32_t lb = lrow < RV ? (uint32_t)(wave * 64 + lane) * 16u : 0x80000000u;
+        asm volatile("" : "+v"(lb));
+        for (;;) {
+#pragma unroll
+            for (int j = 0; j < UPW; ++j)
+                x[j] = hx_get2(rx, base + lb + (uint32_t)(j * NW * 64 * 16));
+            bool ok = true;
+#pragma unroll
+            for (int j = 0; j < UPW; ++j)
+                ok &= ((x[j].y >> 16) == tag) & ((x[j].w >> 16) == tag);
+            ok |= lrow >= RV;
+            if (__all(ok)) break;
+            if (hx_spin_fail(spins, a.err, lane, 1, a.spin_limit)) break;
+        }
+#pragma unroll
+        for (int j = 0; j < UPW; ++j) {
+            bf16x8 af;
+            __builtin_memcpy(&af, &x[j], 16);
+#pragma unroll
+            for (int i = 0; i < NTB; ++i) Mma<bf16>::run(acc[i], af, wf[j][i]);
+        }
+        float* rb = red + (size_t)((par * 2 + k) * KW + wave) * NTB * 4 * PS + lane;
+#pragma unroll
+        for (int i = 0; i < NTB; ++i)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) rb[(i * 4 + e) * PS] = acc[i][e];
+    };
+    auto reduce = [&](int par, int k) {                 // in-order sum over the waves
+        const int ln = (r >> 2) * 16 + (uu & 15), ii = r & 3, tile = uu >> 4;
+        const float* rb = red + (size_t)(par * 2 + k) * KW * NTB * 4 * PS + ii * PS + ln;
+        float pr[NW], s = 0.f;
+#pragma unroll
+        for (int kw = 0; kw < NW; ++kw) pr[kw] = rb[(kw * NTB + tile) * 4 * PS];
+#pragma unroll
+        for (int kw = 0; kw < NW; ++kw) s += pr[kw];
+        return s;
+    };
+    // (the lane's granule index is re-made opaque per step, so no 64-bit slot pointer is
+    //  carried across the step loop: it spilled at MT = 4)
+    uint32_t pslot = ((uint32_t)((unit >> 3) * 64 + ((unit & 7) >> 1) * 16 + r) << 1) + (unit & 1);
+    auto publish = [&](int t, int m, const GruBwdPoint& o) {
+        if (!(a.withhold && blockIdx.x == 0)) {
+            u64* dst = a.xg + (size_t)(t & 1) * bufw + (size_t)(g * MT + m) * RG * D + pslot;
+            const u64 v = (u64)__bfloat16_as_ushort(__float2bfloat16(o.dar)) |
+                          ((u64)__bfloat16_as_ushort(__float2bfloat16(o.daz)) << 16) |
+                          ((u64)__bfloat16_as_ushort(__float2bfloat16(o.dghn)) << 32) |
+                          ((u64)(uint32_t)(a.Fr - t) << 48);
+            if (local) __hip_atomic_store(dst, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            else __hip_atomic_store(dst, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    };
+    auto store = [&](int t, int m, float cdar, float cdaz, float cdghn, float cdan, float cddir,
+                     float* q) {
+        const int row = row_of(m);
+        if (rv && row < B && !(a.exp & 1)) {
+            const int64_t ob = (int64_t)row * a.ldd + (int64_t)t * a.sd;
+            if (a.dgh) {
+                float* dg = a.dgh + ob;
+                dg[unit] = cdar; dg[D + unit] = cdaz; dg[2 * D + unit] = cdghn;
+            }
+            unsigned short* dl = reinterpret_cast<unsigned short*>(a.dgh_lp + ob);
+            const unsigned short har = __bfloat16_as_ushort(__float2bfloat16(cdar)),
+                                 haz = __bfloat16_as_ushort(__float2bfloat16(cdaz)),
+                                 hgn = __bfloat16_as_ushort(__float2bfloat16(cdghn)),
+                                 han = __bfloat16_as_ushort(__float2bfloat16(cdan));
+            const bool nts = !(a.exp & 2048);
+            if (nts) {
+                __builtin_nontemporal_store(har, dl + unit);
+                __builtin_nontemporal_store(haz, dl + D + unit);
+                __builtin_nontemporal_store(hgn, dl + 2 * D + unit);
+            } else {
+                dl[unit] = har; dl[D + unit] = haz; dl[2 * D + unit] = hgn;
+            }
+            if (a.dgi) {
+                float* di = a.dgi + ob;
+                di[unit] = cdar; di[D + unit] = cdaz; di[2 * D + unit] = cdan;
+            }
+            if (a.dgi_lp) {
+                unsigned short* dj = reinterpret_cast<unsigned short*>(a.dgi_lp + ob);
+                if (nts) {
+                    __builtin_nontemporal_store(har, dj + unit);
+                    __builtin_nontemporal_store(haz, dj + D + unit);
+                    __builtin_nontemporal_store(han, dj + 2 * D + unit);
+                } else {
+                    dj[unit] = har; dj[D + unit] = haz; dj[2 * D + unit] = han;
+                }
+            }
+            q[NTHR] += cdar; q[2 * NTHR] += cdaz; q[3 * NTHR] += cdghn; q[4 * NTHR] += cdan;
+            if (t == 0) a.ddir0[(int64_t)row * D + unit] = cddir;
+        }
+    };
+    for (int t = a.Fr - 1; t >= 0; --t) {
+    asm volatile("" : "+v"(rop), "+v"(pslot));
+#pragma unroll 1
+    for (int m0 = 0; m0 < MT; m0 += 2) {
+        const bool has_next = t + 1 < a.Fr;
+        float* q0 = sl + (m0 * 5) * NTHR + tid;
+        float* q1 = q0 + 5 * NTHR;
+        const int par = ((a.Fr - 1 - t) * (MT / 2) + m0 / 2) & 1;
+        float s0 = 0.f, s1 = 0.f;
+        if (has_next) {
+            poll_mma(t, m0, par, 0);
+            poll_mma(t, m0 + 1, par, 1);
+            __syncthreads();
+            s0 = reduce(par, 0);
+            s1 = reduce(par, 1);
+        }
+        float dh0 = s0 + dyv, dh1 = s1 + dy1;
+        if (has_next) { dh0 += q0[0]; dh1 += q1[0]; }
+        const GruBwdPoint o0 = gru_bwd_point(dh0, gr, gz, gn, gg, hp);
+        const GruBwdPoint o1 = gru_bwd_point(dh1, gr1, gz1, gn1, gg1, hp1);
+        q0[0] = o0.ddir;
+        q1[0] = o1.ddir;
+        publish(t, m0, o0);
+        publish(t, m0 + 1, o1);
+        if (!(a.exp & 64)) {                       // (timing: SRNN_GX_EXP 64 skips the fetch)
+            if (m0 + 2 < MT) {
+                fetch(t, m0 + 2, dyv, gr, gz, gn, gg, hp);
+                fetch(t, m0 + 3, dy1, gr1, gz1, gn1, gg1, hp1);
+            } else if (t > 0) {
+                fetch(t - 1, 0, dyv, gr, gz, gn, gg, hp);
+                fetch(t - 1, 1, dy1, gr1, gz1, gn1, gg1, hp1);
+            }
+        }
+        store(t, m0, o0.dar, o0.daz, o0.dghn, o0.dan, o0.ddir, q0);
+        store(t, m0 + 1, o1.dar, o1.daz, o1.dghn, o1.dan, o1.ddir, q1);
+    }
+    }
+    rop = r;                            // (the epilogue's rows: not the loop's opaque copy)
+    } else {
     for (int t = a.Fr - 1; t >= 0; --t) {
     asm volatile("" : "+v"(rop));
 #pragma unroll 1
@@ -858,6 +1015,7 @@ __global__ __launch_bounds__(gx::NTHR, 2) void gru_xcd_bwd_pk_kernel(GruXBwdArgs
             }
             if (t == 0) a.ddir0[(int64_t)row * D + unit] = o.ddir;
         }
+    }
     }
     }
 #pragma unroll
@@ -1129,14 +1287,24 @@ extern "C" int srnn_gru_xcd_bwd2(int dtype, int B, int D, int Fr, const float* d
              gru_xcd_bwd_pk_kernel<12, 4>},
             {gru_xcd_bwd_pk_kernel<16, 1>, gru_xcd_bwd_pk_kernel<16, 2>,
              gru_xcd_bwd_pk_kernel<16, 4>}};
+        // MT > 1: the batched form (two tiles per phase: 11.5 -> 8.9 us per step at 512 rows;
+        // SRNN_GX_BATCH=0: one tile per phase, for A/B and tests); its reduction buffers hold
+        // two tiles' partials
+        static const PkK kpb[4][3] = {
+            {nullptr, gru_xcd_bwd_pk_kernel<4, 2, 2>, gru_xcd_bwd_pk_kernel<4, 4, 2>},
+            {nullptr, gru_xcd_bwd_pk_kernel<8, 2, 2>, gru_xcd_bwd_pk_kernel<8, 4, 2>},
+            {nullptr, gru_xcd_bwd_pk_kernel<12, 2, 2>, gru_xcd_bwd_pk_kernel<12, 4, 2>},
+            {nullptr, gru_xcd_bwd_pk_kernel<16, 2, 2>, gru_xcd_bwd_pk_kernel<16, 4, 2>}};
         const int mi = L.mt == 1 ? 0 : L.mt == 2 ? 1 : 2;
-        const PkK k = kp[D / 256 - 1][mi];
-        static bool attr[4][3] = {};
-        if (!attr[D / 256 - 1][mi]) {
+        const int bi = kpb[D / 256 - 1][mi] && env_flag("SRNN_GX_BATCH", 1) ? 1 : 0;
+        const PkK k = bi ? kpb[D / 256 - 1][mi] : kp[D / 256 - 1][mi];
+        if (bi) lds += (size_t)2 * KW * 2 * 4 * gx::PS * 4;
+        static bool attr[2][4][3] = {};
+        if (!attr[bi][D / 256 - 1][mi]) {
             SRNN_CHECK_HIP(hipFuncSetAttribute((const void*)k,
                                                hipFuncAttributeMaxDynamicSharedMemorySize,
                                                160 * 1024));
-            attr[D / 256 - 1][mi] = true;
+            attr[bi][D / 256 - 1][mi] = true;
         }
         if (srnn_persist_check((const void*)k, gx::NTHR, lds, (int64_t)a.G * a.P, "gru_xcd_bwd"))
             return 1;
