@@ -456,6 +456,45 @@ int srnn_generate3(const SrnnModel* m, int n_seqs, int n_cond, const float* cond
                    const float* row_bias, const float* noise, uint64_t seed, int row0,
                    int64_t* seq, float* logp, void* workspace, size_t workspace_bytes, int flags,
                    void* stream, const float* temperature, const int32_t* top_k);
+/* srnn_generate3 with a per-row nucleus (top-p) cut-off as the third control:
+ *   top_p       (n_seqs) fp32 device array or NULL (= 1, off, for every row).  Domain: 0 < p <= 1.
+ * Everything srnn_generate3 states stays; S is its top-k set.  For tau > 0 and p < 1:
+ *   w_j = exp((z_j - max z) / tau) for j in S,  W = sum_S w_j
+ *   N   = {j in S : z_j >= v_p}, v_p the LARGEST logit value v with
+ *         sum_{j in S, z_j >= v} w_j >= p W
+ *         (the smallest set of most probable classes whose tempered mass, renormalised over S,
+ *          reaches p: the class that crosses p is included, ties at v_p are all kept)
+ *   x   = argmax_{j in N} (z_j - tau log q_j), first index on ties
+ * tau = 0 (greedy) ignores p; p = 1 skips the select and the row's draw is srnn_generate3's, bit
+ * for bit.  Masses are compared in integer fixed point (u_j = rint(2^22 w_j), exact sums): a
+ * normalised partial mass is off by less than 1e-4, and the comparison is
+ * the same in every kernel.  The kernels do not validate: p outside (0, 1), or NaN, is treated
+ * as off; callers check the domain (model.nucleus_control does).  Noise consumption and `logp`
+ * are unchanged.  top_p NULL: exactly srnn_generate3 (same kernels).  top_p given: the samplers'
+ * level-2 instantiations run, whichever of temperature / top_k are given, and the persistent
+ * loop's co-residency check is made on that instantiation.                                  */
+int srnn_generate4(const SrnnModel* m, int n_seqs, int n_cond, const float* cond,
+                   const float* row_bias, const float* noise, uint64_t seed, int row0,
+                   int64_t* seq, float* logp, void* workspace, size_t workspace_bytes, int flags,
+                   void* stream, const float* temperature, const int32_t* top_k,
+                   const float* top_p);
+/* srnn_gen_persistent_rows for a call at sampling-control level `level`: 0 none (the plain
+ * plan), 1 temperature / top_k (srnn_gen_persistent_rows_ctrl), 2 with top_p.  Other levels: 0. */
+int srnn_gen_persistent_rows_level(int dtype, int n_seqs, int dim, int fs0, int q_levels,
+                                   int level);
+/* The engine's row sampler on caller-chosen logits: one draw per row, by the same device
+ * functions as srnn_generate4's loops, at the control level the arrays imply (all NULL: the
+ * plain draw of srnn_generate).
+ *   logits      (rows, 256) fp32, leading dimension ld >= 256 floats; rows 16-byte aligned
+ *   noise       (rows, 256) fp32 Exp(1) draws (contiguous, 16-byte aligned), or NULL to draw
+ *               from Philox4x32-10 with (seed, row0, step): the counters the loop uses for global
+ *               row row0 + b at generation step `step` (seed, row0 and step are otherwise unused)
+ *   temperature / top_k / top_p   (rows) device arrays or NULL, as in srnn_generate4
+ *   index       (rows) int64, output
+ *   logp        optional (rows, 256) fp32: log_softmax(logits), whatever the controls        */
+int srnn_sample_rows(const float* logits, int64_t ld, int rows, const float* noise, uint64_t seed,
+                     int row0, int step, const float* temperature, const int32_t* top_k,
+                     const float* top_p, int64_t* index, float* logp, void* stream);
 
 #ifdef __cplusplus
 }

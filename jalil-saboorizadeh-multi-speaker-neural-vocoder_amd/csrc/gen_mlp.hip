@@ -247,11 +247,11 @@ __device__ __forceinline__ void gmt_grid_barrier(int* bar, int nblk, int epoch, 
 // masks of the runtime shape would otherwise be scalar-register spills in the loop.
 // TG: the bottom tick's GEMM runs in this launch before the sample loop (GenMlpArgs::tg;
 // bf16 only), with the prologue's resident-fragment loads in flight beside it.
-// CT: the draw takes the rows' sampling controls (GenMlpArgs::temperature / top_k) -- builds
-// of their own, launched only when a control array is given: without one the kernels that run
-// are the plain ones, unchanged.
+// CT: the level of the rows' sampling controls in the draw -- 1: GenMlpArgs::temperature /
+// top_k, 2: those and top_p -- builds of their own, launched only when a control array of that
+// level is given: without one the kernels that run are the plain ones (0), unchanged.
 template <typename T, int UPW, int NT, int NZT, int MAXT, int FS0C, int DC, bool TG = false,
-          bool CT = false>
+          int CT = 0>
 __global__ __launch_bounds__(gm::NTHR, 2) void gen_mlp_kernel(GenMlpArgs a) {
     using F = typename GmT<T>::frag;
     constexpr int GV = GmT<T>::GV, UK = GmT<T>::UK, EPL = UK / 4;
@@ -278,7 +278,8 @@ __global__ __launch_bounds__(gm::NTHR, 2) void gen_mlp_kernel(GenMlpArgs a) {
     const T* wol = (const T*)((char*)gsh + 16);
     // CT: the group's rows' sampling controls {tau, k} x 8 rows sit at the very end of the
     // dynamic LDS (read once in the prologue: the loop holds neither array's pointer nor the
-    // values in registers -- it has none to spare -- and no other offset moves)
+    // values in registers -- it has none to spare -- and no other offset moves); CT = 2: the
+    // rows' p x 8 follow them (96 B in all)
     int* ctl = (int*)((char*)gsh + 16 + (WOL ? (size_t)NZ * (D + 8) * sizeof(T) : 0) +
                       (TG ? (size_t)gmt::LDS : 0));
     const int p = blockIdx.x / a.G;
@@ -627,12 +628,14 @@ __global__ __launch_bounds__(gm::NTHR, 2) void gen_mlp_kernel(GenMlpArgs a) {
         const int j = i0 - FS0 + k;
         hist[r * gm::HIST + (j & (gm::HIST - 1))] = (int)a.seq[(int64_t)b * a.ldseq + j];
     }
-    if constexpr (CT) {
+    if constexpr (CT != 0) {
         // the rows' controls (R <= 8: one a1 element per thread); a null array = its default
         if (tid < min(R, 8)) {
             const int b = min(g * R + tid, B - 1);
             ctl[2 * tid] = (int)__float_as_uint(a.temperature ? a.temperature[b] : 1.0f);
             ctl[2 * tid + 1] = a.top_k ? a.top_k[b] : 0;
+            if constexpr (CT == 2)
+                ctl[16 + tid] = (int)__float_as_uint(a.top_p ? a.top_p[b] : 1.0f);
         }
     }
     // this thread's a1/a2 element
@@ -665,7 +668,7 @@ __global__ __launch_bounds__(gm::NTHR, 2) void gen_mlp_kernel(GenMlpArgs a) {
         tg[6] = a.tk->hp[(int64_t)tb * D + tu];
     };
     // (CT too: the controlled draw takes their place in the register budget)
-    if (!WOL && !CT && a.tk && tr < R && tb < B && tu < D) {
+    if (!WOL && CT == 0 && a.tk && tr < R && tb < B && tu < D) {
         const float* gr = a.tk->G + (int64_t)tb * a.tk->ldg;
         const float* hr = a.tk->gh + (int64_t)tb * a.tk->ldgh;
         tg[0] = gr[tu]; tg[1] = gr[D + tu]; tg[2] = gr[2 * D + tu];
@@ -910,12 +913,16 @@ __global__ __launch_bounds__(gm::NTHR, 2) void gen_mlp_kernel(GenMlpArgs a) {
             float* lrow = (p == 0 && valid && a.logp)
                               ? a.logp + ((int64_t)(i - a.L) * B + b) * Q : nullptr;
             int x;
-            if constexpr (CT) {
+            if constexpr (CT != 0) {
                 // the row's controls, from LDS (tau scales log q at the point of use, so lq
                 // keeps its meaning whether drawn ahead or here)
                 const int rc = __builtin_amdgcn_readfirstlane(min(r, 7));
                 const int2 ck = *reinterpret_cast<const int2*>(ctl + 2 * rc);
-                x = sample_row_ctrl(v, lq, __uint_as_float((uint32_t)ck.x), ck.y, lrow, lane);
+                if constexpr (CT == 2)
+                    x = sample_row_ctrl(v, lq, __uint_as_float((uint32_t)ck.x), ck.y,
+                                        __uint_as_float((uint32_t)ctl[16 + rc]), lrow, lane);
+                else
+                    x = sample_row_ctrl(v, lq, __uint_as_float((uint32_t)ck.x), ck.y, lrow, lane);
             } else {
                 x = sample_row(v, lq, lrow, lane);
             }
@@ -944,7 +951,7 @@ __global__ __launch_bounds__(gm::NTHR, 2) void gen_mlp_kernel(GenMlpArgs a) {
         const GenMlpArgs::Tick* tk = a.tk;
         asm volatile("" : "+s"(tk));            // fresh loads of the table after the loop
         if (tr < R && tb < B && tu < D) {
-            if (WOL || CT) load_tick();
+            if (WOL || CT != 0) load_tick();
             const int inx = i0 + a.nsteps;
             const float* mr = tk->fmin + (int64_t)tu * 16;
             const float* mz = tk->fmin + (int64_t)(D + tu) * 16;
@@ -1026,7 +1033,7 @@ __global__ void gen_wfrag_kernel(const char* __restrict__ w, int64_t ld_bytes, i
 namespace {
 typedef void (*GmKernel)(GenMlpArgs);
 
-template <typename T, int MAXT, int FS0C, bool CT>
+template <typename T, int MAXT, int FS0C, int CT>
 GmKernel pick_t(int upw, int nzt) {
     if (upw <= 1 && nzt <= 16) return gen_mlp_kernel<T, 1, 4, 16, MAXT, FS0C, 0, false, CT>;
     if (upw <= 2 && nzt <= 4) return gen_mlp_kernel<T, 2, 4, 4, MAXT, FS0C, 0, false, CT>;
@@ -1034,7 +1041,7 @@ GmKernel pick_t(int upw, int nzt) {
     return nullptr;     // other fp32 shapes at D > 512 would spill their resident weights
 }
 // MAXT = older taps gathered per sample (FS0 - 1 <= MAXT); CT = the sampling-control builds
-template <typename T, bool CT>
+template <typename T, int CT>
 GmKernel pick(int upw, int nzt, int fs0, int D, int R) {
     // (FS0 = 16, the bottom frame of every published config, gets its own build: a
     //  constant FS0 folds the tap bookkeeping that would otherwise live in scalar registers;
@@ -1079,11 +1086,14 @@ int gen_mlp_plan(int dtype, int B, int D, int FS0, int Q, int ctrl, GenMlpPlan* 
     if (!R) return 0;
     // (the kernels recorded here are the ones gen_mlp_launch starts and asks the occupancy
     //  of: with controls, their own instantiations)
+    if (ctrl < 0 || ctrl > 2) return 0;
     const GmKernel k = dtype == SRNN_BF16
-                           ? (ctrl ? pick<bf16, true>(upw, NZ / 16, FS0, D, R)
-                                   : pick<bf16, false>(upw, NZ / 16, FS0, D, R))
-                           : (ctrl ? pick<float, true>(upw, NZ / 16, FS0, D, R)
-                                   : pick<float, false>(upw, NZ / 16, FS0, D, R));
+                           ? (ctrl == 2   ? pick<bf16, 2>(upw, NZ / 16, FS0, D, R)
+                              : ctrl == 1 ? pick<bf16, 1>(upw, NZ / 16, FS0, D, R)
+                                          : pick<bf16, 0>(upw, NZ / 16, FS0, D, R))
+                           : (ctrl == 2   ? pick<float, 2>(upw, NZ / 16, FS0, D, R)
+                              : ctrl == 1 ? pick<float, 1>(upw, NZ / 16, FS0, D, R)
+                                          : pick<float, 0>(upw, NZ / 16, FS0, D, R));
     if (!k) return 0;
     // the in-launch tick GEMM variant (bf16, the compiled D = 1024 / FS0 = 16 shape);
     // SRNN_GEN_TICK_GEMM=0 keeps the bottom tick's GEMM a launch of its own
@@ -1092,8 +1102,9 @@ int gen_mlp_plan(int dtype, int B, int D, int FS0, int Q, int ctrl, GenMlpPlan* 
     if (dtype == SRNN_BF16 && FS0 == 16 && D == 1024 && R == 8 && Q == gm::Q &&
         env_flag("SRNN_GEN_TICK_GEMM", 1))
         pl->kernel_tg =
-            ctrl ? (const void*)gen_mlp_kernel<bf16, 4, 4, 2, 15, 16, 1024, true, true>
-                 : (const void*)gen_mlp_kernel<bf16, 4, 4, 2, 15, 16, 1024, true>;
+            ctrl == 2   ? (const void*)gen_mlp_kernel<bf16, 4, 4, 2, 15, 16, 1024, true, 2>
+            : ctrl == 1 ? (const void*)gen_mlp_kernel<bf16, 4, 4, 2, 15, 16, 1024, true, 1>
+                        : (const void*)gen_mlp_kernel<bf16, 4, 4, 2, 15, 16, 1024, true>;
     const int es = dtype == SRNN_BF16 ? 2 : 4;
     const int KW = NU < gm::NW ? NU : gm::NW;
     const int ntm = (CW / 16) > (NZ / 16) ? CW / 16 : NZ / 16;
@@ -1101,7 +1112,7 @@ int gen_mlp_plan(int dtype, int B, int D, int FS0, int Q, int ctrl, GenMlpPlan* 
     lds += (size_t)KW * ntm * 32 * 16;                // rows 0..7 of the 16-row tiles (R = 8)
     lds += (size_t)R * gm::HIST * 4;
     lds += 16;                                        // group / member / mode words
-    if (ctrl) lds += 64;                              // the rows' controls (gen_mlp_kernel CT)
+    if (ctrl) lds += ctrl == 2 ? 96 : 64;             // the rows' controls (gen_mlp_kernel CT)
     if (dtype == SRNN_F32 && upw > 4)                 // W_out slice in LDS (gen_mlp_kernel WOL)
         lds += (size_t)NZ * (D + 8) * 4;
     if (lds > 160 * 1024) return 0;
@@ -1112,7 +1123,7 @@ int gen_mlp_plan(int dtype, int B, int D, int FS0, int Q, int ctrl, GenMlpPlan* 
     pl->ok = 1;
     pl->local = env_flag("SRNN_GEN_LOCAL", 1);
     pl->dtype = dtype;
-    pl->ctrl = ctrl ? 1 : 0;
+    pl->ctrl = ctrl;
     pl->R = R;
     pl->G = cdiv(B, R);
     pl->P = P;
@@ -1222,7 +1233,7 @@ int gen_mlp_launch(const GenMlpPlan* pl, GenMlpArgs a, hipStream_t s) {
     // SRNN_GEN_LOCAL=0 only forces the global-mode hand-offs
     SRNN_REQUIRE(a.census && pl->G * pl->P <= HX_KEYED_WORDS, "gen_mlp: no census array");
     a.nolocal = pl->local ? 0 : 1;
-    SRNN_REQUIRE((pl->ctrl != 0) == (a.temperature || a.top_k),
+    SRNN_REQUIRE(pl->ctrl == (a.top_p ? 2 : (a.temperature || a.top_k) ? 1 : 0),
                  "gen_mlp: plan and sampling-control arrays disagree");
     {
         // SRNN_GEN_DIAG=1: phase timestamps of the first launch into a device buffer that

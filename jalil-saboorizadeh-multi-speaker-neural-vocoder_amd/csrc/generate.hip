@@ -24,7 +24,8 @@ int srnn_mlp_l1_impl(int dtype, const void* tab, const int64_t* x, int64_t ldx, 
 int srnn_sample_impl(const float* z, int64_t ldz, int B, const float* noise, uint64_t seed,
                      int row0,
                      const int* base, int off, int L, int64_t* seq, int64_t ldseq,
-                     float* logp_out, const float* temperature, const int* top_k, hipStream_t s);
+                     float* logp_out, const float* temperature, const int* top_k,
+                     const float* top_p, hipStream_t s);
 int srnn_gru_cell_impl(int dtype, int B, int D, int Din, const void* x, int64_t ldx,
                        const void* wih, const float* bih, const float* gi, int64_t ldgi,
                        const void* h, int64_t ldh, const float* hf, int64_t ldhf, const void* whh,
@@ -465,6 +466,7 @@ struct Ctx {
     float* logp;
     const float* temperature = nullptr;   // per-row sampling controls (device, n_seqs), or null
     const int* top_k = nullptr;
+    const float* top_p = nullptr;         // nucleus mass (device, n_seqs), or null
     hipStream_t s;
     const GenMlpPlan* pl;     // persistent sample loop, or null for per-sample kernels
     // lq holds the draws of block-relative steps [noise_beg, noise_end): drawn ahead by the
@@ -655,7 +657,7 @@ int mlp_step(Ctx& c, int off) {
     RET(linear_fwd(dt, SRNN_F32, B, Q, D, c.b.a2, D, m->w_out, D, m->b_out, c.b.logits, Q, 0,
                    c.s));
     RET(srnn_sample_impl(c.b.logits, Q, B, c.noise, c.seed, c.row0, c.b.base, off, c.L, c.seq, c.ldseq,
-                         c.logp, c.temperature, c.top_k, c.s));
+                         c.logp, c.temperature, c.top_k, c.top_p, c.s));
     return 0;
 }
 
@@ -688,7 +690,7 @@ int run_block(Ctx& c, int periods) {
             a.B = c.B; a.D = m->dim; a.FS0 = m->tier[0].frame_size;
             a.xa1 = c.b.xa1; a.xa2 = c.b.xa2; a.xz = c.b.xz; a.err = c.b.gerr;
             a.census = c.b.gerr + 64;
-            a.temperature = c.temperature; a.top_k = c.top_k;
+            a.temperature = c.temperature; a.top_k = c.top_k; a.top_p = c.top_p;
             if (c.b.lq && env_flag("SRNN_GEN_NOISE_AHEAD", 1)) {
                 // drawn ahead by a tick's input launch, else by a launch here
                 if (off < c.noise_beg || off + a.nsteps > c.noise_end) {
@@ -736,14 +738,22 @@ extern "C" int srnn_gen_persistent_rows(int dtype, int n_seqs, int dim, int fs0,
     return pl.R;
 }
 
-// the same for a call with sampling controls (srnn_generate3 with an array): the controlled
-// instantiation's plan, which takes 64 B more LDS
-extern "C" int srnn_gen_persistent_rows_ctrl(int dtype, int n_seqs, int dim, int fs0,
-                                             int q_levels) {
+// the same for a call with sampling controls: the plan of the controlled instantiations of
+// `level` (1: srnn_generate3 / 4 with temperature or top_k, 64 B more LDS; 2: srnn_generate4
+// with top_p, 96 B more; 0: the plain plan)
+extern "C" int srnn_gen_persistent_rows_level(int dtype, int n_seqs, int dim, int fs0,
+                                              int q_levels, int level) {
     GenMlpPlan pl;
-    if (!gen_mlp_plan(dtype, n_seqs, dim, fs0, q_levels, 1, &pl) || !env_flag("SRNN_GEN_PERSIST", 1))
+    if (level < 0 || level > 2) return 0;
+    if (!gen_mlp_plan(dtype, n_seqs, dim, fs0, q_levels, level, &pl) ||
+        !env_flag("SRNN_GEN_PERSIST", 1))
         return 0;
     return pl.R;
+}
+
+extern "C" int srnn_gen_persistent_rows_ctrl(int dtype, int n_seqs, int dim, int fs0,
+                                             int q_levels) {
+    return srnn_gen_persistent_rows_level(dtype, n_seqs, dim, fs0, q_levels, 1);
 }
 
 extern "C" int srnn_gen_workspace_size(const SrnnModel* m, int n_seqs, size_t* bytes) {
@@ -755,26 +765,27 @@ extern "C" int srnn_gen_workspace_size(const SrnnModel* m, int n_seqs, size_t* b
     return 0;
 }
 
-extern "C" int srnn_generate3(const SrnnModel* m, int n_seqs, int n_cond, const float* cond,
+extern "C" int srnn_generate4(const SrnnModel* m, int n_seqs, int n_cond, const float* cond,
                               const float* row_bias, const float* noise, uint64_t seed,
                               int row0, int64_t* seq, float* logp, void* workspace,
                               size_t workspace_bytes, int flags, void* stream,
-                              const float* temperature, const int32_t* top_k);
+                              const float* temperature, const int32_t* top_k,
+                              const float* top_p);
 
 extern "C" int srnn_generate(const SrnnModel* m, int n_seqs, int n_cond, const float* cond,
                              const float* row_bias, const float* noise, uint64_t seed,
                              int64_t* seq, float* logp, void* workspace, size_t workspace_bytes,
                              int flags, void* stream) {
-    return srnn_generate3(m, n_seqs, n_cond, cond, row_bias, noise, seed, 0, seq, logp,
-                          workspace, workspace_bytes, flags, stream, nullptr, nullptr);
+    return srnn_generate4(m, n_seqs, n_cond, cond, row_bias, noise, seed, 0, seq, logp,
+                          workspace, workspace_bytes, flags, stream, nullptr, nullptr, nullptr);
 }
 
 extern "C" int srnn_generate2(const SrnnModel* m, int n_seqs, int n_cond, const float* cond,
                               const float* row_bias, const float* noise, uint64_t seed,
                               int row0, int64_t* seq, float* logp, void* workspace,
                               size_t workspace_bytes, int flags, void* stream) {
-    return srnn_generate3(m, n_seqs, n_cond, cond, row_bias, noise, seed, row0, seq, logp,
-                          workspace, workspace_bytes, flags, stream, nullptr, nullptr);
+    return srnn_generate4(m, n_seqs, n_cond, cond, row_bias, noise, seed, row0, seq, logp,
+                          workspace, workspace_bytes, flags, stream, nullptr, nullptr, nullptr);
 }
 
 // srnn_generate2 with per-row sampling controls (sampler.hpp sample_row_ctrl): with both
@@ -785,6 +796,19 @@ extern "C" int srnn_generate3(const SrnnModel* m, int n_seqs, int n_cond, const 
                               int row0, int64_t* seq, float* logp, void* workspace,
                               size_t workspace_bytes, int flags, void* stream,
                               const float* temperature, const int32_t* top_k) {
+    return srnn_generate4(m, n_seqs, n_cond, cond, row_bias, noise, seed, row0, seq, logp,
+                          workspace, workspace_bytes, flags, stream, temperature, top_k, nullptr);
+}
+
+// srnn_generate3 with the rows' nucleus mass (sampler.hpp, the (tau, k, p) sample_row_ctrl):
+// top_p given selects the level-2 instantiations, planned and checked as such; top_p null
+// launches exactly what srnn_generate3 launches.
+extern "C" int srnn_generate4(const SrnnModel* m, int n_seqs, int n_cond, const float* cond,
+                              const float* row_bias, const float* noise, uint64_t seed,
+                              int row0, int64_t* seq, float* logp, void* workspace,
+                              size_t workspace_bytes, int flags, void* stream,
+                              const float* temperature, const int32_t* top_k,
+                              const float* top_p) {
     SRNN_REQUIRE(row0 >= 0, "generate: negative row offset");
     SRNN_REQUIRE(m && n_seqs > 0 && n_cond > 0 && seq && workspace, "generate: bad args");
     SRNN_REQUIRE(m->n_tiers >= 1 && m->n_tiers <= SRNN_MAX_TIERS, "generate: n_tiers");
@@ -794,7 +818,7 @@ extern "C" int srnn_generate3(const SrnnModel* m, int n_seqs, int n_cond, const 
     Ctx c;
     c.m = m;
     GenMlpPlan pl;
-    plan_for(m, n_seqs, (temperature || top_k) ? 1 : 0, &pl);
+    plan_for(m, n_seqs, top_p ? 2 : (temperature || top_k) ? 1 : 0, &pl);
     if (flags & 2) pl.ok = 0;          // caller asked for the per-sample kernel path
     size_t need = carve(m, n_seqs, (char*)workspace, &c.b, &pl);
     SRNN_REQUIRE(workspace_bytes >= need, "generate: workspace %zu < %zu", workspace_bytes, need);
@@ -811,6 +835,7 @@ extern "C" int srnn_generate3(const SrnnModel* m, int n_seqs, int n_cond, const 
     c.logp = logp;
     c.temperature = temperature;
     c.top_k = top_k;
+    c.top_p = top_p;
     c.pl = pl.ok ? &pl : nullptr;
     c.tick_gemm = c.pl && c.b.fold &&
                   gen_mlp_tick_gemm_ok(&pl, (m->tier[0].frame_size + 3) * m->dim, m->dim, n_seqs);

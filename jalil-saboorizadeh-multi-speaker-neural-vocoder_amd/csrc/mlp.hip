@@ -614,14 +614,30 @@ extern "C" int srnn_nll_bwd(const int64_t* target, int64_t ldt, int Tlen, int64_
 // ------------------------------------------------------------------ sampler
 // One wave per row; lane holds q = 4 * lane + j (16-B loads of logits and noise).  The
 // per-row math lives in sampler.hpp, shared with the persistent generation loop.
-// CT: the row's sampling controls (temperature[b], top_k[b]; either array may be null = that
-// control at its default) go into the draw; without them the kernel is the plain sampler.
-template <bool CT>
+// CT: the level of the row's sampling controls in the draw -- 0 none (the plain sampler),
+// 1 temperature[b] / top_k[b], 2 those and top_p[b]; a null array = that control at its
+// default.
+template <int CT>
+__device__ __forceinline__ int sample_draw(const floatx4& v, const floatx4& lq, int b,
+                                           const float* temperature, const int* top_k,
+                                           const float* top_p, float* lrow, int lane) {
+    if constexpr (CT == 2)
+        return sample_row_ctrl(v, lq, temperature ? temperature[b] : 1.0f, top_k ? top_k[b] : 0,
+                               top_p ? top_p[b] : 1.0f, lrow, lane);
+    else if constexpr (CT == 1)
+        return sample_row_ctrl(v, lq, temperature ? temperature[b] : 1.0f, top_k ? top_k[b] : 0,
+                               lrow, lane);
+    else
+        return sample_row(v, lq, lrow, lane);
+}
+
+template <int CT>
 __global__ __launch_bounds__(256) void sample_kernel(
     const float* __restrict__ z, int64_t ldz, int B, const float* __restrict__ noise,
     uint64_t seed, int row0, const int* __restrict__ base, int off, int L,
     int64_t* __restrict__ seq, int64_t ldseq, float* __restrict__ logp_out,
-    const float* __restrict__ temperature, const int* __restrict__ top_k) {
+    const float* __restrict__ temperature, const int* __restrict__ top_k,
+    const float* __restrict__ top_p) {
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (b >= B) return;
@@ -630,25 +646,55 @@ __global__ __launch_bounds__(256) void sample_kernel(
     const floatx4 v = *reinterpret_cast<const floatx4*>(z + (int64_t)b * ldz + 4 * lane);
     const floatx4 lq = log_noise(sample_noise(noise, seed, B, b, step, lane, row0));
     float* lrow = logp_out ? logp_out + ((int64_t)step * B + b) * 256 : nullptr;
-    int bi;
-    if constexpr (CT)
-        bi = sample_row_ctrl(v, lq, temperature ? temperature[b] : 1.0f, top_k ? top_k[b] : 0,
-                             lrow, lane);
-    else
-        bi = sample_row(v, lq, lrow, lane);
+    const int bi = sample_draw<CT>(v, lq, b, temperature, top_k, top_p, lrow, lane);
     if (lane == 0) seq[(int64_t)b * ldseq + i] = bi;
 }
 
 int srnn_sample_impl(const float* z, int64_t ldz, int B, const float* noise, uint64_t seed,
                      int row0, const int* base, int off, int L, int64_t* seq, int64_t ldseq,
-                     float* logp_out, const float* temperature, const int* top_k, hipStream_t s) {
-    if (temperature || top_k)
-        hipLaunchKernelGGL(sample_kernel<true>, dim3(cdiv(B, 4)), dim3(256), 0, s, z, ldz, B, noise,
-                           seed, row0, base, off, L, seq, ldseq, logp_out, temperature, top_k);
-    else
-        hipLaunchKernelGGL(sample_kernel<false>, dim3(cdiv(B, 4)), dim3(256), 0, s, z, ldz, B,
-                           noise, seed, row0, base, off, L, seq, ldseq, logp_out, temperature,
-                           top_k);
+                     float* logp_out, const float* temperature, const int* top_k,
+                     const float* top_p, hipStream_t s) {
+    auto k = top_p ? sample_kernel<2> : (temperature || top_k) ? sample_kernel<1>
+                                                                : sample_kernel<0>;
+    hipLaunchKernelGGL(k, dim3(cdiv(B, 4)), dim3(256), 0, s, z, ldz, B, noise, seed, row0, base,
+                       off, L, seq, ldseq, logp_out, temperature, top_k, top_p);
+    SRNN_LAUNCH_CHECK();
+    return 0;
+}
+
+// The stand-alone row sampler (srnn_sample_rows): one draw per row of caller-chosen logits, by
+// the same sampler.hpp functions at the control level the arrays imply.  noise: a (B, 256)
+// Exp(1) buffer, or null for the Philox stream of global row row0 + b at generation step
+// `step` -- the counters the loops above use.
+template <int CT>
+__global__ __launch_bounds__(256) void sample_rows_kernel(
+    const float* __restrict__ z, int64_t ldz, int B, const float* __restrict__ noise,
+    uint64_t seed, int row0, int step, int64_t* __restrict__ idx, float* __restrict__ logp_out,
+    const float* __restrict__ temperature, const int* __restrict__ top_k,
+    const float* __restrict__ top_p) {
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (b >= B) return;
+    const floatx4 v = *reinterpret_cast<const floatx4*>(z + (int64_t)b * ldz + 4 * lane);
+    const floatx4 lq = log_noise(sample_noise(noise, seed, B, b, noise ? 0 : step, lane, row0));
+    float* lrow = logp_out ? logp_out + (int64_t)b * 256 : nullptr;
+    const int bi = sample_draw<CT>(v, lq, b, temperature, top_k, top_p, lrow, lane);
+    if (lane == 0) idx[b] = bi;
+}
+
+extern "C" int srnn_sample_rows(const float* logits, int64_t ld, int rows, const float* noise,
+                                uint64_t seed, int row0, int step, const float* temperature,
+                                const int32_t* top_k, const float* top_p, int64_t* index,
+                                float* logp, void* stream) {
+    SRNN_REQUIRE(logits && index && rows > 0, "sample_rows: bad args");
+    SRNN_REQUIRE(ld >= 256 && ld % 4 == 0 && ((uintptr_t)logits & 15) == 0,
+                 "sample_rows: logits rows must be 16-byte aligned (ld %lld)", (long long)ld);
+    SRNN_REQUIRE(((uintptr_t)noise & 15) == 0, "sample_rows: noise must be 16-byte aligned");
+    SRNN_REQUIRE(row0 >= 0 && step >= 0, "sample_rows: negative row offset or step");
+    auto k = top_p ? sample_rows_kernel<2> : (temperature || top_k) ? sample_rows_kernel<1>
+                                                                    : sample_rows_kernel<0>;
+    hipLaunchKernelGGL(k, dim3(cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, logits, ld, rows,
+                       noise, seed, row0, step, index, logp, temperature, top_k, top_p);
     SRNN_LAUNCH_CHECK();
     return 0;
 }

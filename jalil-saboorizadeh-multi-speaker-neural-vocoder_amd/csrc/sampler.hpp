@@ -226,3 +226,98 @@ __device__ __forceinline__ int sample_row_ctrl(const floatx4& v, const floatx4& 
     if (logp_row) row_logp(z, logp_row, lane);
     return bi;
 }
+
+// ---- nucleus (top-p), per row -------------------------------------------------------------
+// Extends the definition above; S, tau and the draw keep their meaning.  For tau > 0 and
+// 0 < p < 1 (anything else, NaN included, is "off"):
+//   w_j = exp((z_j - max z) / tau) for j in S,  W = sum_S w_j
+//   N = {j in S : z_j >= v_p},  v_p the LARGEST logit value v with
+//       sum_{j in S, z_j >= v} w_j >= p W
+//   (the smallest set of most probable classes whose tempered mass, renormalised over S,
+//    reaches p: the class that crosses p is in, ties at v_p are all kept, as for k)
+//   x = argmax_{j in N} (z_j - tau log q_j)
+// Mass arithmetic: integer fixed point, u_j = rint(2^22 w_j) (0 outside S).  The largest class
+// has u = 2^22 and 256 weights sum to at most 2^30, so every partial sum is an exact 32-bit
+// integer whatever the order of the reduction, and the test is  sum >= T,
+// T = max(1, ceil(p * float(U))), U = sum u_j.  (Error bound of a normalised partial mass:
+// DESIGN.md §3.)
+
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
+    v += dpp_u32<0xB1>(v);
+    v += dpp_u32<0x4E>(v);
+    v += dpp_u32<0x141>(v);
+    v += dpp_u32<0x140>(v);
+    uint32_t lo, hi;
+    xpair16(v, lo, hi);
+    v = lo + hi;
+    xpair32(v, lo, hi);
+    return lo + hi;
+}
+
+// Key of v_p for a row held as keys (4 per lane), vk the top-k threshold (-inf: k off), tau > 0,
+// 0 < p < 1, all wave-uniform.  Wave-level like wave_kth_largest_key -- no LDS, no barrier, no
+// early exit, 32 steps -- but a step's count is a weighted one: 4 compare-selects and adds per
+// lane, an integer wave sum and a scalar select.  The predicate "mass of {key >= c} >= T" is
+// monotone in c and true at c = 0 (U >= T), so the bits found from the top give the largest
+// such c: the key of the crossing class.  Live across the loop: the 4 keys and their 4 weights.
+// Classes outside S weigh 0, so the result is never below vk.  All 64 lanes must be active.
+__device__ __forceinline__ uint32_t wave_nucleus_key(const uint32_t (&key)[4], float vk,
+                                                     float tau, float p) {
+    float z[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) z[j] = key_float(key[j]);
+    const float m = wave_max(fmaxf(fmaxf(z[0], z[1]), fmaxf(z[2], z[3])));
+    uint32_t u[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        u[j] = z[j] >= vk ? (uint32_t)__builtin_rintf(4194304.0f * expf((z[j] - m) / tau)) : 0u;
+    const uint32_t U =
+        __builtin_amdgcn_readfirstlane(wave_sum_u32((u[0] + u[1]) + (u[2] + u[3])));
+    uint32_t T = (uint32_t)__builtin_ceilf(p * (float)U);
+    T = T < 1u ? 1u : T;
+    uint32_t t = 0;
+#pragma unroll
+    for (int bit = 31; bit >= 0; --bit) {
+        const uint32_t c = t | (1u << bit);
+        const uint32_t s = ((key[0] >= c ? u[0] : 0u) + (key[1] >= c ? u[1] : 0u)) +
+                           ((key[2] >= c ? u[2] : 0u) + (key[3] >= c ? u[3] : 0u));
+        t = __builtin_amdgcn_readfirstlane(wave_sum_u32(s)) >= T ? c : t;
+    }
+    return t;
+}
+
+// sample_row_ctrl with the row's top_p as well (tau, k, p wave-uniform).  Both selects run on
+// the row held as keys in place of the logits; each is skipped by a wave-uniform branch when
+// its control is off, and with p off the draw is sample_row_ctrl(v, lq, tau, k)'s, bit for bit.
+// tau <= 0 (greedy) ignores p.  The allowed set is the float compare z_j >= max(v_k, v_p).
+__device__ __forceinline__ int sample_row_ctrl(const floatx4& v, const floatx4& lq, float tau,
+                                               int k, float p, float* logp_row, int lane) {
+    tau = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(tau)));
+    k = __builtin_amdgcn_readfirstlane(k);
+    p = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(p)));
+    const bool ksel = k >= 1 && k <= 255;
+    const bool psel = p > 0.f && p < 1.f && tau > 0.f;
+    floatx4 z = v;
+    float vk = -__builtin_inff();
+    if (ksel || psel) {
+        uint32_t key[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) key[j] = float_key(z[j]);
+        // (opaque to the compiler, or it would keep the logits live beside their keys)
+        asm volatile("" : "+v"(key[0]), "+v"(key[1]), "+v"(key[2]), "+v"(key[3]));
+        if (ksel) vk = key_float(wave_kth_largest_key(key, k));
+        if (psel) vk = key_float(wave_nucleus_key(key, vk, tau, p));
+#pragma unroll
+        for (int j = 0; j < 4; ++j) z[j] = key_float(key[j]);
+    }
+    floatx4 t;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        // (tau <= 0: greedy, the noise is not read -- log q may be -inf)
+        const float sc = tau > 0.f ? __builtin_fmaf(-tau, lq[j], z[j]) : z[j];
+        t[j] = z[j] >= vk ? sc : -__builtin_inff();
+    }
+    const int bi = row_argmax(t, lane);
+    if (logp_row) row_logp(z, logp_row, lane);
+    return bi;
+}

@@ -15,6 +15,8 @@ The drop-in classes call these ops, so the registered ops ARE the product path:
   srnn::step_advance_           the device step counters srnn::adam_clip_ can read (graph mode)
   srnn::generate                Generator.__call__'s sample loop (model.py:445-520)
   srnn::generate_ctrl           the same loop with per-row temperature / top-k in the draw
+  srnn::generate_ctrl_p         ... and a per-row nucleus (top-p) cut-off
+  srnn::sample_rows             the loops' row sampler on caller-chosen logits
 
 Every op has a fake (meta) kernel, so FakeTensor / torch.compile tracing sees shapes without
 running HIP code, and the differentiable ones have their autograd formula attached with
@@ -398,7 +400,7 @@ def _(dstep):
 
 # ------------------------------------------------------------------ generation
 def _generate(weights, meta, cond, row_bias, noise, seed, row_offset, flags, return_logp,
-              temperature=None, top_k=None):
+              temperature=None, top_k=None, top_p=None):
     import ctypes
     import model
     m = model.srnn_model_struct(weights, meta)
@@ -415,7 +417,9 @@ def _generate(weights, meta, cond, row_bias, noise, seed, row_offset, flags, ret
     args = (ctypes.byref(m), n_seqs, num_cond, H.ptr(cond), H.ptr(row_bias), H.ptr(noise),
             int(seed) & ((1 << 64) - 1), int(row_offset), H.ptr(seq),
             H.ptr(logp) if return_logp else None, H.ptr(ws), sz.value, int(flags), H.stream())
-    if temperature is None and top_k is None:
+    if top_p is not None:
+        H.lib().call('srnn_generate4', *args, H.ptr(temperature), H.ptr(top_k), H.ptr(top_p))
+    elif temperature is None and top_k is None:
         H.lib().call('srnn_generate2', *args)
     else:
         H.lib().call('srnn_generate3', *args, H.ptr(temperature), H.ptr(top_k))
@@ -446,6 +450,14 @@ def _(weights, meta, cond, row_bias, noise, seed, row_offset, flags, return_logp
     return _generate_fake(meta, cond, return_logp)
 
 
+def _check_rows(op, n_seqs, dev, *arrays):
+    for name, t, dt in arrays:
+        if (t.dtype != dt or t.dim() != 1 or t.shape[0] != n_seqs or not t.is_contiguous() or
+                t.device != dev):
+            raise ValueError('%s: %s must be a contiguous (%d,) %s tensor on %s'
+                             % (op, name, n_seqs, dt, dev))
+
+
 @torch.library.custom_op('srnn::generate_ctrl', mutates_args=())
 def generate_ctrl(weights: list[Tensor], meta: list[int], cond: Tensor, row_bias: Tensor,
                   noise: Optional[Tensor], seed: int, row_offset: int, flags: int,
@@ -454,12 +466,8 @@ def generate_ctrl(weights: list[Tensor], meta: list[int], cond: Tensor, row_bias
     temperature (n_seqs,) float32, finite and >= 0 (0 = greedy); top_k (n_seqs,) int32 in
     [0, Q] (0 and Q = off).  model.sampling_controls validates and builds both.  The returned
     log-probs stay the model's own log-softmax, not the tempered / truncated distribution."""
-    n_seqs = cond.shape[0]
-    for name, t, dt in (('temperature', temperature, torch.float32), ('top_k', top_k, torch.int32)):
-        if (t.dtype != dt or t.dim() != 1 or t.shape[0] != n_seqs or not t.is_contiguous() or
-                t.device != cond.device):
-            raise ValueError('generate_ctrl: %s must be a contiguous (%d,) %s tensor on %s'
-                             % (name, n_seqs, dt, cond.device))
+    _check_rows('generate_ctrl', cond.shape[0], cond.device,
+                ('temperature', temperature, torch.float32), ('top_k', top_k, torch.int32))
     return _generate(weights, meta, cond, row_bias, noise, seed, row_offset, flags, return_logp,
                      temperature, top_k)
 
@@ -470,5 +478,70 @@ def _(weights, meta, cond, row_bias, noise, seed, row_offset, flags, return_logp
     return _generate_fake(meta, cond, return_logp)
 
 
+@torch.library.custom_op('srnn::generate_ctrl_p', mutates_args=())
+def generate_ctrl_p(weights: list[Tensor], meta: list[int], cond: Tensor, row_bias: Tensor,
+                    noise: Optional[Tensor], seed: int, row_offset: int, flags: int,
+                    return_logp: bool, temperature: Tensor, top_k: Tensor,
+                    top_p: Tensor) -> tuple[Tensor, Tensor]:
+    """srnn::generate_ctrl with the rows' nucleus mass as well (srnn_generate4): top_p (n_seqs,)
+    float32 in (0, 1] (1 = off), which model.nucleus_control validates and builds.  The draw is
+    then taken over the smallest set of most probable classes of the top-k set whose tempered
+    mass reaches top_p (the crossing class included, ties kept)."""
+    _check_rows('generate_ctrl_p', cond.shape[0], cond.device,
+                ('temperature', temperature, torch.float32), ('top_k', top_k, torch.int32),
+                ('top_p', top_p, torch.float32))
+    return _generate(weights, meta, cond, row_bias, noise, seed, row_offset, flags, return_logp,
+                     temperature, top_k, top_p)
+
+
+@generate_ctrl_p.register_fake
+def _(weights, meta, cond, row_bias, noise, seed, row_offset, flags, return_logp, temperature,
+      top_k, top_p):
+    return _generate_fake(meta, cond, return_logp)
+
+
+@torch.library.custom_op('srnn::sample_rows', mutates_args=())
+def sample_rows(logits: Tensor, noise: Optional[Tensor], seed: int, row0: int, step: int,
+                temperature: Optional[Tensor], top_k: Optional[Tensor],
+                top_p: Optional[Tensor], return_logp: bool) -> tuple[Tensor, Tensor]:
+    """One draw per row of logits (rows, 256) float32 (row stride a multiple of 4 floats) by the
+    generation loops' sampler (srnn_sample_rows): ((rows,) int64 indices, (rows, 256) float32
+    log_softmax(logits) or empty).  noise (rows, 256) float32 Exp(1) or None = Philox with
+    (seed, row0, step); temperature / top_k / top_p (rows,) float32 / int32 / float32 or None,
+    at whose level the draw runs (all None: the plain draw)."""
+    if (logits.dim() != 2 or logits.shape[1] != 256 or logits.dtype != torch.float32 or
+            not logits.is_cuda or logits.stride(1) != 1 or logits.shape[0] < 1):
+        raise ValueError('sample_rows: logits must be a (rows, 256) float32 device tensor with '
+                         'unit column stride')
+    rows, dev = logits.shape[0], logits.device
+    if rows > 1 and (logits.stride(0) < 256 or logits.stride(0) % 4):
+        raise ValueError('sample_rows: logits row stride must be >= 256 and a multiple of 4')
+    if noise is not None and (noise.shape != (rows, 256) or noise.dtype != torch.float32 or
+                              noise.device != dev or not noise.is_contiguous()):
+        raise ValueError('sample_rows: noise must be a contiguous (%d, 256) float32 tensor on %s'
+                         % (rows, dev))
+    if row0 < 0 or step < 0:
+        raise ValueError('sample_rows: row0 and step must be >= 0')
+    _check_rows('sample_rows', rows, dev,
+                *[(n, t, dt) for n, t, dt in (('temperature', temperature, torch.float32),
+                                              ('top_k', top_k, torch.int32),
+                                              ('top_p', top_p, torch.float32)) if t is not None])
+    idx = torch.empty(rows, device=dev, dtype=torch.int64)
+    logp = torch.empty((rows, 256) if return_logp else (0,), device=dev, dtype=torch.float32)
+    H.lib().call('srnn_sample_rows', H.ptr(logits), logits.stride(0) if rows > 1 else 256, rows,
+                 H.ptr(noise), int(seed) & ((1 << 64) - 1), int(row0), int(step),
+                 H.ptr(temperature), H.ptr(top_k), H.ptr(top_p), H.ptr(idx),
+                 H.ptr(logp) if return_logp else None, H.stream())
+    return idx, logp
+
+
+@sample_rows.register_fake
+def _(logits, noise, seed, row0, step, temperature, top_k, top_p, return_logp):
+    rows = logits.shape[0]
+    return (logits.new_empty((rows,), dtype=torch.int64),
+            logits.new_empty((rows, 256) if return_logp else (0,)))
+
+
 OPS = ('tier_fwd', 'tier_bwd', 'mlp_fwd', 'mlp_bwd', 'nll_bits', 'nll_bits_bwd', 'upsample',
-       'upsample_bwd', 'dequant', 'adam_clip_', 'step_advance_', 'generate', 'generate_ctrl')
+       'upsample_bwd', 'dequant', 'adam_clip_', 'step_advance_', 'generate', 'generate_ctrl',
+       'generate_ctrl_p', 'sample_rows')

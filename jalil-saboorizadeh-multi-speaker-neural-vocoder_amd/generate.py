@@ -19,6 +19,8 @@ Two sampling modes:
 Beyond the reference: --temperature T (default 1.0) and --top_k K (default 0 = off) set the
 Generator's sampling controls for every row of every call -- the draw becomes
 argmax(z - T log q) over the K largest logits; --temperature 0 is greedy (no randomness).
+--top_p P (default 1.0 = off, 0 < P <= 1) cuts the draw further to the nucleus: the most
+probable classes whose tempered mass reaches P.
 At the defaults the run is the reference's draw, bit for bit as before.
 """
 import argparse
@@ -66,6 +68,7 @@ default_params = {
     'compute_dtype': 'fp32',
     'temperature': 1.0,
     'top_k': 0,
+    'top_p': 1.0,
 }
 
 
@@ -183,7 +186,8 @@ def main(frame_sizes, **params):
             rows[j * n:(j + 1) * n, :c.shape[0]] = c
             spks[j * n:(j + 1) * n] = jobs[j][1]
         gen = Generator(model, use_cuda)
-        ctrl = dict(temperature=params['temperature'], top_k=params['top_k'])
+        ctrl = dict(temperature=params['temperature'], top_k=params['top_k'],
+                    top_p=params['top_p'])
         if world > 1:
             # rank-sharded: contiguous row shards gathered at the end (rows
             # padded to a multiple of the world size); either sampler reproduces the
@@ -216,7 +220,8 @@ def main(frame_sizes, **params):
         gen = Generator(model, use_cuda)
         samples = gen(params['n_samples'], params['sample_length'], cond, speaker,
                       sampler=params['sampler'], seed=params['seed'],
-                      temperature=params['temperature'], top_k=params['top_k']).numpy()
+                      temperature=params['temperature'], top_k=params['top_k'],
+                      top_p=params['top_p']).numpy()
         for i in range(params['n_samples']):
             write_wav(fname, samples[i, :], sr=params['sample_rate'])
 
@@ -245,7 +250,7 @@ def build_parser():
                       ('static_spk', parse_bool), ('seed', int), ('weight_norm', parse_bool),
                       ('cond_list', str), ('spk_list', str), ('sampler', str),
                       ('batch_files', parse_bool), ('compute_dtype', str),
-                      ('temperature', float), ('top_k', int)):
+                      ('temperature', float), ('top_k', int), ('top_p', float)):
         p.add_argument('--' + name, type=typ)
     # gen.sh passes --results_path (generate.py has no such option; accepted and ignored)
     p.add_argument('--results_path', type=str)

@@ -1009,6 +1009,31 @@ def sampling_controls(n_seqs, temperature=1.0, top_k=0, q_levels=256):
     return torch.from_numpy(t32.copy()), torch.from_numpy(k.astype(np.int32))
 
 
+def nucleus_control(n_seqs, top_p=1.0):
+    """The per-row nucleus (top-p) control of Generator.__call__ as a host tensor (a pure host
+    function, beside sampling_controls).
+
+    top_p is a scalar (broadcast to every row) or a per-row sequence, array or tensor of length
+    n_seqs; every value must be finite with 0 < p <= 1 (1 = off).  Returns None when every row
+    is 1, else an (n_seqs,) float32 tensor.  Raises ValueError otherwise."""
+    a = top_p.detach().cpu().numpy() if torch.is_tensor(top_p) else np.asarray(top_p)
+    if a.dtype == object or a.dtype.kind not in 'biuf':
+        raise ValueError('nucleus_control: top_p must be numeric')
+    if a.ndim == 0:
+        a = np.broadcast_to(a, (n_seqs,))
+    if a.ndim != 1 or a.shape[0] != n_seqs:
+        raise ValueError('nucleus_control: top_p has shape %s, expected a scalar or (%d,)'
+                         % (tuple(a.shape), n_seqs))
+    p32 = a.astype(np.float64).astype(np.float32)
+    # (checked as the float32 the device reads: a p that rounds to 1 is off, one that rounds
+    #  to 0 is out of the domain)
+    if not np.all(np.isfinite(p32)) or np.any(p32 <= 0) or np.any(p32 > 1):
+        raise ValueError('nucleus_control: top_p must be finite with 0 < top_p <= 1')
+    if np.all(p32 == 1.0):
+        return None
+    return torch.from_numpy(p32.copy())
+
+
 class Generator(Runner):
     """model.py:439-520: autoregressive generation, the whole loop on the device.
 
@@ -1031,6 +1056,11 @@ class Generator(Runner):
     consumes is unchanged, so a row at the defaults inside a mixed batch reproduces its
     uncontrolled stream.  With return_logp the log-probs stay the model's own log-softmax of
     the logits, NOT the tempered or truncated distribution that was drawn from.
+
+    top_p (nucleus_control: a scalar or one value per row, 0 < p <= 1, 1 = off) cuts the draw
+    further, to the smallest set of most probable classes of the top-k set whose tempered mass
+    exp((z - max z) / temperature), renormalised over that set, reaches top_p: the class that
+    crosses top_p is included and ties at the cut are kept.  Greedy rows ignore it.
     """
 
     def __init__(self, model, cuda=False):
@@ -1040,12 +1070,13 @@ class Generator(Runner):
 
     def __call__(self, n_seqs, seq_len, cond, spk, sampler='torch', seed=0, noise=None,
                  return_logp=False, use_graph=True, dtype=None, persistent=True, row_offset=0,
-                 temperature=1.0, top_k=0):
+                 temperature=1.0, top_k=0, top_p=1.0):
         """row_offset: these n_seqs rows are rows [row_offset, row_offset + n_seqs) of a larger
         batch (rank-sharded generation, see shard_generate): the Philox noise (sampler='philox')
         is that of the global rows, so shards reproduce the single-process stream.
-        temperature, top_k: the sampling controls (class docstring); at their defaults the call
-        is the uncontrolled one, op and kernels.  return_logp's log-probs are the model's
+        temperature, top_k, top_p: the sampling controls (class docstring); at their defaults
+        the call is the uncontrolled one, op and kernels, and with top_p at 1 it is the call
+        without top_p.  return_logp's log-probs are the model's
         log-softmax whatever the controls."""
         model = self.model
         self.reset_hidden_states()
@@ -1064,6 +1095,9 @@ class Generator(Runner):
         T = num_cond * L
         Q = model.q_levels
         ctrl = sampling_controls(n_seqs, temperature, top_k, Q)
+        nucleus = nucleus_control(n_seqs, top_p)
+        if nucleus is not None and ctrl is None:
+            ctrl = (torch.ones(n_seqs, dtype=torch.float32), torch.zeros(n_seqs, dtype=torch.int32))
         weights, meta = generation_weights(model, dtype)
         row_bias = top_row_bias(model, spk)
         if noise is None and sampler == 'torch':
@@ -1079,6 +1113,9 @@ class Generator(Runner):
                     bool(return_logp))
             if ctrl is None:
                 seq, logp = torch.ops.srnn.generate(*args)
+            elif nucleus is not None:
+                seq, logp = torch.ops.srnn.generate_ctrl_p(*args, ctrl[0].to(dev), ctrl[1].to(dev),
+                                                           nucleus.to(dev))
             else:
                 seq, logp = torch.ops.srnn.generate_ctrl(*args, ctrl[0].to(dev), ctrl[1].to(dev))
         assert utils.q_zero(Q) == Q // 2
@@ -1104,8 +1141,8 @@ def shard_generate(generator, n_seqs, cond, spk, seed, rank=None, world=None, sa
         size): the draw is then (T, noise_rows, Q), as the unpadded single-process run makes
         it, and the padding rows get unit noise (their output is discarded).
     cond: (num_cond, C) shared or (n_seqs, num_cond, C) per row; spk: int or (n_seqs,).
-    temperature / top_k (Generator's sampling controls): scalars or one value per row of the
-    whole batch; per-row values are sliced to the rank's rows like spk.
+    temperature / top_k / top_p (Generator's sampling controls): scalars or one value per row of
+    the whole batch; per-row values are sliced to the rank's rows like spk.
     seq_len is accepted like Generator's (the reference ignores it, model.py:455).
     Returns the host float32 (n_seqs, num_cond * lookback) batch."""
     import distributed as Dd
@@ -1125,6 +1162,9 @@ def shard_generate(generator, n_seqs, cond, spk, seed, rank=None, world=None, sa
                              generator.model.q_levels)
     if ctrl is not None:
         kw['temperature'], kw['top_k'] = ctrl[0][rows], ctrl[1][rows]
+    nucleus = nucleus_control(n_seqs, kw.pop('top_p', 1.0))
+    if nucleus is not None:
+        kw['top_p'] = nucleus[rows]
     if sampler == 'torch' and kw.get('noise') is None:
         model = generator.model
         nr = n_seqs if noise_rows is None else int(noise_rows)

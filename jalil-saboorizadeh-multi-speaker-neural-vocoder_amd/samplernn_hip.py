@@ -96,6 +96,8 @@ _SIGS = {
     'srnn_generate': [_P, _I, _I, _P, _P, _P, _U64, _P, _P, _P, _SZ, _I, _P],
     'srnn_generate2': [_P, _I, _I, _P, _P, _P, _U64, _I, _P, _P, _P, _SZ, _I, _P],
     'srnn_generate3': [_P, _I, _I, _P, _P, _P, _U64, _I, _P, _P, _P, _SZ, _I, _P, _P, _P],
+    'srnn_generate4': [_P, _I, _I, _P, _P, _P, _U64, _I, _P, _P, _P, _SZ, _I, _P, _P, _P, _P],
+    'srnn_sample_rows': [_P, _L, _I, _P, _U64, _I, _I, _P, _P, _P, _P, _P, _P],
     'srnn_persistent_flag_to_f32': [_P, _P],
     'srnn_persistent_flag_or_f32': [_P, _P],
     'srnn_persistent_flag_snapshot': [_P, _P],
@@ -197,6 +199,7 @@ def lib():
 def exported_symbols():
     return sorted(_SIGS) + ['srnn_last_error', 'srnn_abi_version', 'srnn_gru_seq_supported',
                             'srnn_gen_persistent_rows', 'srnn_gen_persistent_rows_ctrl',
+                            'srnn_gen_persistent_rows_level',
                             'srnn_gru_xcd_work_bytes',
                             'srnn_gru_xcd_bwd_work_bytes', 'srnn_gru_xcd_error',
                             'srnn_persistent_error_take', 'srnn_gemm_amax_taken',
@@ -379,11 +382,37 @@ def gru_xcd_bwd_work_bytes(dtype, B, D):
 
 def gen_persistent_rows(dtype, n_seqs, dim, fs0, q_levels=256, ctrl=False):
     """Rows per group of the persistent generation loop for this shape (0: per-sample
-    kernels); ctrl: of a call with sampling controls (the controlled build's plan)."""
-    fn = lib().dll.srnn_gen_persistent_rows_ctrl if ctrl else lib().dll.srnn_gen_persistent_rows
+    kernels); ctrl: of a call with sampling controls (the controlled build's plan) -- True or 1
+    with temperature / top_k, 2 with top_p as well."""
+    level = int(ctrl)
+    if level not in (0, 1, 2):
+        raise ValueError('gen_persistent_rows: ctrl must be False, True, 1 or 2')
+    if level == 2:
+        fn = lib().dll.srnn_gen_persistent_rows_level
+        fn.argtypes = [_I, _I, _I, _I, _I, _I]
+        fn.restype = _I
+        return int(fn(dcode(dtype), n_seqs, dim, fs0, q_levels, 2))
+    fn = lib().dll.srnn_gen_persistent_rows_ctrl if level else lib().dll.srnn_gen_persistent_rows
     fn.argtypes = [_I, _I, _I, _I, _I]
     fn.restype = _I
     return int(fn(dcode(dtype), n_seqs, dim, fs0, q_levels))
+
+
+def sample_rows(logits, noise=None, seed=0, row0=0, step=0, temperature=None, top_k=None,
+                top_p=None, return_logp=False):
+    """One draw per row of `logits` (rows, 256) by the engine's sampler (the registered op
+    srnn::sample_rows -> srnn_sample_rows: the device functions of the generation loops, at
+    the control level the arrays imply).  noise: (rows, 256) Exp(1) draws, or None for the
+    Philox stream of global row row0 + b at generation step `step` under `seed`.  temperature
+    / top_k / top_p: None or one value per row (float32 / int32 / float32 tensors; see
+    model.sampling_controls and model.nucleus_control for the domains -- the kernel does not
+    validate).  Returns the (rows,) int64 indices, with return_logp also the (rows, 256)
+    log_softmax(logits)."""
+    import custom_ops  # noqa: F401  (registers the op)
+    idx, logp = torch.ops.srnn.sample_rows(logits, noise, int(seed) & ((1 << 63) - 1), int(row0),
+                                           int(step), temperature, top_k, top_p,
+                                           bool(return_logp))
+    return (idx, logp) if return_logp else idx
 
 
 _GRU_SEQ = {}

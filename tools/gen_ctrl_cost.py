@@ -4,6 +4,8 @@ D = 1024 (bench.py's `gen` line), the same process and model, alternating
     off      temperature 1, top-k off      (srnn::generate, the plain kernels)
     tau      temperature 0.7 on every row  (srnn::generate_ctrl, the controlled builds)
     tau+k    temperature 0.7, top_k 16
+    tau+p    temperature 0.7, top_p 0.9    (srnn::generate_ctrl_p, the level-2 builds)
+    tau+k+p  temperature 0.7, top_k 16, top_p 0.9
 
   python tools/gen_ctrl_cost.py [n_cond] [rounds] [dtype]  > bench_out/gen_ctrl_cost.txt
 
@@ -22,7 +24,9 @@ import torch  # noqa: E402
 
 import bench  # noqa: E402
 
-MODES = (('off', {}), ('tau', dict(temperature=0.7)), ('tau+k', dict(temperature=0.7, top_k=16)))
+MODES = (('off', {}), ('tau', dict(temperature=0.7)), ('tau+k', dict(temperature=0.7, top_k=16)),
+         ('tau+p', dict(temperature=0.7, top_p=0.9)),
+         ('tau+k+p', dict(temperature=0.7, top_k=16, top_p=0.9)))
 
 
 def main():
@@ -48,11 +52,11 @@ def main():
             gen(B, 0, cond, spk, sampler='philox', seed=5, **kw)
             torch.cuda.synchronize()
             us[name].append((time.perf_counter() - t0) / steps * 1e6)
-            print('round %d %-6s %.4f us/sample' % (r, name, us[name][-1]), flush=True)
+            print('round %d %-7s %.4f us/sample' % (r, name, us[name][-1]), flush=True)
     base = float(np.median(us['off']))
     for name, _ in MODES:
         v = np.array(us[name])
-        print('%-6s median %.4f us/sample (min %.4f max %.4f), %+.4f vs off; %d samples x %d rows,'
+        print('%-7s median %.4f us/sample (min %.4f max %.4f), %+.4f vs off; %d samples x %d rows,'
               ' %s' % (name, np.median(v), v.min(), v.max(), np.median(v) - base, steps, B,
                        str(dtype).replace('torch.', '')))
 
