@@ -48,8 +48,14 @@ int srnn_udequantize2d(const int64_t* k, int64_t ldk, float* out, int rows, int 
  * C = act(alpha * op(A) . op(B) + beta * Cin + bias)  (bias_mode 1: per column, 2: per row)
  * Replaces the Conv1d(k=1) / nn.Linear / GRU-input / ConvTranspose1d matmuls of
  * model.py:85-116,148-178,287-301 and nn.py:12-43 (forward, dgrad and wgrad).
- * tile = -1 picks the tile shape from the problem size.  mask (optional, input dtype,
- * row stride ldmask) zeroes outputs where mask <= 0 (the ReLU backward of model.py:320-321). */
+ * tile = -1 picks the backend and tile shape from the problem; a tile code that names one
+ * backend (3 ring, 4 skinny, 5 256-tile, 6 thin) forces it, and the call fails with a "not
+ * eligible" error -- C untouched -- when that backend cannot serve the problem (a batch,
+ * its shape or alignment rules); 0 / 1 / 2 force the general kernel's 128 / 64 / 32 tile.
+ * mask (optional, input dtype, row stride ldmask) zeroes outputs where mask <= 0 (the ReLU
+ * backward of model.py:320-321); in a batch, mask's batch stride is strideC, as C's (there
+ * is no stride argument of its own), whatever ldmask is.  beta == 0 never reads Cin, even
+ * when it is given.  K == 0 gives act(beta * Cin + bias). */
 int srnn_gemm(int dtype, int out_dtype, int transA, int transB, int M, int N, int K,
               float alpha, const void* A, int64_t lda, int64_t strideA, const void* B,
               int64_t ldb, int64_t strideB, float beta, const float* Cin, int64_t ldcin,

@@ -180,6 +180,11 @@ int srnn_try_blaslt(const GemmProblem& q, hipStream_t s) {
     //  266 us -- but inside the step the library form measured 0.1-0.2 ms per step faster)
     if (out_dtype == SRNN_F32 && K < env_flag("SRNN_BLASLT_F32_MINK", 0)) return -1;
     if (M % 16 || N % 16 || K % 16 || lda % 8 || ldb % 8 || ldc % 8) return -1;
+    // 16-byte bases, as every vector backend here asks: the library's interface documents an
+    // alignment only for its workspace, so what its kernels assume of A / B / C / bias is not
+    // established; anything else stays on the project's own kernels
+    if ((uintptr_t)A % 16 || (uintptr_t)B % 16 || (uintptr_t)C % 16 || (bias && (uintptr_t)bias % 16))
+        return -1;
     const int epi = bias ? (relu ? HIPBLASLT_EPILOGUE_RELU_BIAS : HIPBLASLT_EPILOGUE_BIAS)
                          : (relu ? HIPBLASLT_EPILOGUE_RELU : HIPBLASLT_EPILOGUE_DEFAULT);
     static std::map<Key, Plan> plans;

@@ -35,6 +35,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g) {
     const T* B = reinterpret_cast<const T*>(g.B) + (int64_t)bz * g.sB;
     TO* Cp = reinterpret_cast<TO*>(g.C) + (int64_t)bz * g.sC;
     const float* Cin = g.Cin ? g.Cin + (int64_t)bz * g.sCin : nullptr;
+    // (a batched mask lies as C does: batch stride sC, its own row stride ldmask)
     const T* mask = g.mask ? reinterpret_cast<const T*>(g.mask) + (int64_t)bz * g.sC : nullptr;
     const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
     floatx4 acc[C::FM][C::FN];
@@ -447,8 +448,9 @@ int srnn_try_general(const GemmProblem& p, hipStream_t s) {
 
 // ---- the router: the backends in the order they are offered a problem.  A row runs when the
 // problem's tile code forces it or leaves the choice open (tile < 0), and its guard holds;
-// a forced backend that does not take the problem is an error.  What no row takes -- and the
-// forced tiles 0 / 1 / 2 -- goes to the general kernel, which takes everything.
+// a forced backend that does not take the problem -- its guard fails (a batch, SRNN_GEMM2=0
+// for code 3) or its own eligibility tests decline -- is an error.  What no row takes -- and
+// the forced tiles 0 / 1 / 2 -- goes to the general kernel, which takes everything.
 struct GemmRoute {
     int code;  // the tile code that forces this backend (-1: none)
     bool (*guard)(const GemmProblem&, bool forced);
@@ -479,7 +481,11 @@ static const GemmRoute kRoutes[] = {
 static int gemm_route(const GemmProblem& p, hipStream_t s) {
     for (const GemmRoute& r : kRoutes) {
         const bool forced = r.code >= 0 && p.tile == r.code;
-        if (!(forced || p.tile < 0) || !r.guard(p, forced)) continue;
+        if (!(forced || p.tile < 0)) continue;
+        if (!r.guard(p, forced)) {
+            SRNN_REQUIRE(!forced, "%s", r.ineligible);
+            continue;
+        }
         const int rc = r.run(p, s);
         if (rc >= 0) return rc;
         SRNN_REQUIRE(!forced, "%s", r.ineligible);

@@ -509,7 +509,12 @@ def gemm(a, b, transA=False, transB=False, out=None, out_dtype=torch.float32, bi
          mask_bits=None, bits_out=None):
     """C = act(alpha op(A) op(B) + beta Cin + bias) on row-major 2-D views (or strided batches).
     mask_bits / bits_out: the ReLU mask as bits (relu_bits buffers), read in place of `mask` /
-    written for C (batch 1)."""
+    written for C (batch 1).
+    mask: row stride mask.stride(0); in a batch its batch stride is sC, as the output's (so a
+    batched mask is laid out as `out` is, rows apart by its own stride).  beta == 0 never reads
+    cin; K == 0 gives act(beta cin + bias).  tile >= 3 forces one backend and raises ("not
+    eligible") when that backend cannot serve the call, batched calls included; 0 / 1 / 2
+    force a tile of the general kernel, which serves everything."""
     need_cuda(a, b)
     if M is None:
         M = a.shape[1] if transA else a.shape[0]
