@@ -247,6 +247,26 @@ int srnn_gemm_csum_taken(void);
  * request no GEMM took).                                                              */
 int srnn_gemm_logsoftmax_next(void);
 int srnn_gemm_logsoftmax_taken(void);
+/* Backward of the SampleLevelMLP's output layer (model.py:320-324) in one pass over dz and
+ * a2 (bf16, Q = 256, D % 128 == 0, M % 256 == 0; contiguous rows):
+ *   da2[M, D]     = bf16(dz . W_out) * [a2 > 0]  -- wt is W_out^T (D, Q); bit-identical to
+ *                   srnn_gemm's masked bf16 product on the 256 x 256 pair path
+ *   dW[Q, D]      = dz^T . a2  (fp32; per-row-range partials summed in range order:
+ *                   deterministic, no atomics)
+ *   db[Q]         = column sums of dz, summed the same way (db may be NULL: not computed)
+ *   csp[M/128, D] = column sums of the stored da2 per 128-row block, in the order of
+ *                   srnn_gemm_csum_next's epilogue (the caller sums the rows: the hidden
+ *                   layer's bias gradient)
+ * srnn_mlp_out_bwd_ranges returns R, the row ranges a launch uses, or 0 when the shape is
+ * not served.  want > 0: that many, clamped to M / 128.  want = 0: the split-K factor
+ * srnn_gemm gives the dz^T . a2 product on the 256 x 256 path when its k-slices are whole
+ * 128-row blocks -- dW then has that product's bits -- else one workgroup per CU.
+ * srnn_mlp_out_bwd runs with the R so obtained; *taken = 1 if it ran, 0 if the shape or an
+ * operand's alignment is not served (nothing written: the caller runs the separate calls). */
+int srnn_mlp_out_bwd_ranges(int dtype, int64_t M, int D, int Q, int want);
+int srnn_mlp_out_bwd(int dtype, const void* dz, const void* a2, const void* wt, int64_t M, int D,
+                     int Q, void* da2, float* dW, float* db, float* csp, int R, int* taken,
+                     void* stream);
 /* srnn_mlp_dtab3 with blk (device, may be NULL): the column-blocked copy of da
  * (blk[D / 4][B * Tlen][4], srnn_gemm_amax_blk_next) the packed form reads instead of da
  * (whole 128-B lines per load).  Same outputs bit for bit.  A sample histogram skewed past

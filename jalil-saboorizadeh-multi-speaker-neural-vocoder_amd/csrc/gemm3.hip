@@ -1270,6 +1270,8 @@ static int g3_pick_split(int tiles, int K) {
     return best;
 }
 
+int srnn_g3_pick_split(int tiles, int K) { return g3_pick_split(tiles, K); }
+
 // Returns -1 if the shape/layout is not eligible (the router goes on), else the status.
 // tile == 5 (forced): take the path whenever eligible, else only when the 256-tile grid
 // (with split-K) occupies the chip at least as well as the 128-tile kernel would.

@@ -57,6 +57,8 @@ void* srnn_scratch(int slot, size_t bytes);
 // Deterministic split-K support.  srnn_splitk_scratch = srnn_scratch(SRNN_SCRATCH_SPLITK);
 // srnn_splitk_sum writes C[m][n] = sum_z part[z][m][n] in z order (float4 columns:
 // N % 4 == 0, C 16-B aligned, ldc % 4 == 0).
+// the split-K factor srnn_try_gemm3 picks for a plain fp32-out product of `tiles` 256 x 256 tiles
+int srnn_g3_pick_split(int tiles, int K);
 float* srnn_splitk_scratch(size_t bytes);
 int srnn_splitk_sum(const float* part, float* C, int64_t ldc, int M, int N, int ks, hipStream_t s);
 

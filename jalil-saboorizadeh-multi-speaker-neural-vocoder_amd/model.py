@@ -35,7 +35,7 @@ import samplernn_hip as H
 verbose = False
 # (tests) how often a fused side result was consumed, and which recurrence kernels ran
 _STATS = {'fused_colsum': 0, 'fused_lp': 0, 'csum_epi': 0, 'lsm_epi': 0, 'gru_xcd_fwd': 0, 'gru_xcd_bwd': 0, 'gru_seq': 0,
-          'gru_cell_steps': 0, 'gru_cell_bwd_steps': 0}
+          'gru_cell_steps': 0, 'gru_cell_bwd_steps': 0, 'out_bwd_fused': 0}
 
 
 def _default_dtype():
@@ -730,6 +730,37 @@ def mlp_forward(mlp, x, upper, ps):
     return logp.reshape(B, Tl, Q), ctx
 
 
+def _mlp_out_bwd_unfused(T, M, D, Q, dz, a1, a2, m2, W_t, W_out, csum_epi):
+    """The output layer's backward as separate calls (every dtype and shape): (dW_out, db_out,
+    da2, dW_hid, db_hid)."""
+    dev = dz.device
+    dW_out = H.gemm(dz, a2, transA=True)                             # (Q, D)
+    db_out = H.colsum(dz, M, Q)
+    # (M, D) = dz . W_out, through W_out^T (D, Q) when the forward made it
+    Wo, tB = (W_t[1], True) if W_t is not None else (W_out, False)
+    # bf16: the da2 GEMM's epilogue also sums its stored columns per 128-row block (the
+    # hidden layer's bias gradient) -- one pass over da2 fewer than a separate column sum
+    csp = None
+    if csum_epi:
+        csp = torch.empty((M // 128, D), device=dev, dtype=torch.float32)
+        H.lib().call('srnn_gemm_csum_next', H.ptr(csp))
+    ev = H.roof_begin()
+    if m2 is not None:
+        da2 = H.gemm(dz, Wo, transB=tB, mask_bits=m2, out_dtype=T)
+    else:
+        da2 = H.gemm(dz, Wo, transB=tB, mask=a2, out_dtype=T)
+    H.roof_end('mlp_da2_gemm', ev, 2.0 * M * D * Q)
+    if csp is not None and not H.lib().dll.srnn_gemm_csum_taken():
+        csp = None
+    if csp is not None:
+        _STATS['csum_epi'] += 1
+    ev = H.roof_begin()
+    dW_hid = H.gemm(da2, a1, transA=True)                            # (D, D)
+    H.roof_end('mlp_dw_hid_gemm', ev, 2.0 * M * D * D)
+    db_hid = H.colsum(csp, M // 128, D) if csp is not None else H.colsum(da2, M, D)
+    return dW_out, db_out, da2, dW_hid, db_hid
+
+
 def mlp_backward(ctx, dlogp, nll=None):
     """Backward of mlp_forward: (d_upper, [parameter gradients]).  nll = (target, T,
     gscale, g): the log-probs' gradient is sequence_nll_loss_bits' closed form (dlogp is then
@@ -752,35 +783,44 @@ def mlp_backward(ctx, dlogp, nll=None):
         dl = dlogp.reshape(M, Q).float().contiguous()
         H.lib().call('srnn_logsoftmax_bwd', H.ptr(dl), Q, H.ptr(logp), Q, M, Q, H.ptr(dz),
                      H.dcode(T), Q, st())
-    dW_out = H.gemm(dz, a2, transA=True)                             # (Q, D)
-    db_out = H.colsum(dz, M, Q)
     m1, m2 = ctx.bits
     ctx.bits = None
     W_t = ctx.W_t
     ctx.W_t = None
-    # (M, D) = dz . W_out, through W_out^T (D, Q) when the forward made it
-    Wo, tB = (W_t[1], True) if W_t is not None else (W_out, False)
-    # bf16: the da2 GEMM's epilogue also sums its stored columns per 128-row block (the
-    # hidden layer's bias gradient) -- one pass over da2 fewer than a separate column sum
-    csp = None
-    if T == torch.bfloat16 and M % 256 == 0 and os.environ.get('SRNN_CSUM_EPI', '1') != '0':
-        csp = torch.empty((M // 128, D), device=dev, dtype=torch.float32)
-        H.lib().call('srnn_gemm_csum_next', H.ptr(csp))
-    ev = H.roof_begin()
-    if m2 is not None:
-        da2 = H.gemm(dz, Wo, transB=tB, mask_bits=m2, out_dtype=T)
-    else:
-        da2 = H.gemm(dz, Wo, transB=tB, mask=a2, out_dtype=T)
-    H.roof_end('mlp_da2_gemm', ev, 2.0 * M * D * Q)
-    if csp is not None and not H.lib().dll.srnn_gemm_csum_taken():
+    csum_epi = T == torch.bfloat16 and M % 256 == 0 and \
+        os.environ.get('SRNN_CSUM_EPI', '1') != '0'
+    # bf16, Q = 256: da2, dW_out and the hidden bias sums from ONE pass over dz and a2
+    # (srnn_mlp_out_bwd; the separate GEMMs fetch each of dz and a2 again).  The kernel keeps
+    # the separate calls' summation orders, so every gradient keeps its bits; db_out stays
+    # the column pass over dz (the kernel's own db_out sums in another order).
+    # SRNN_OUT_BWD_FUSED=0: the separate calls, which shapes the kernel does not serve (None)
+    # take too.  With a2's mask kept as bits (SRNN_MASK_BITS=1) the kernel still masks by
+    # the a2 it stages for dW_out -- bit m2 is a2 > 0 by construction -- so both settings
+    # return the same bits (test_mask_bits_step_bf16 compares every gradient exactly).
+    fused = None
+    if T == torch.bfloat16 and Q == 256 and D % 128 == 0 and M % 256 == 0 and \
+            W_t is not None and os.environ.get('SRNN_OUT_BWD_FUSED', '1') != '0':
+        ev = H.roof_begin()
+        fused = H.mlp_out_bwd(dz, a2, W_t[1], want_db=False)
+        if fused is not None:
+            # (both products: da2 and dW_out)
+            H.roof_end('mlp_da2_gemm', ev, 4.0 * M * D * Q)
+    if fused is not None:
+        da2, dW_out, _, csp = fused
+        db_out = H.colsum(dz, M, Q)
+        _STATS['out_bwd_fused'] += 1
+        if csum_epi:
+            _STATS['csum_epi'] += 1
+            db_hid = H.colsum(csp, csp.shape[0], D)
+        else:
+            db_hid = H.colsum(da2, M, D)
         csp = None
-    if csp is not None:
-        _STATS['csum_epi'] += 1
-    ev = H.roof_begin()
-    dW_hid = H.gemm(da2, a1, transA=True)                            # (D, D)
-    H.roof_end('mlp_dw_hid_gemm', ev, 2.0 * M * D * D)
-    db_hid = H.colsum(csp, M // 128, D) if csp is not None else H.colsum(da2, M, D)
-    csp = None
+        ev = H.roof_begin()
+        dW_hid = H.gemm(da2, a1, transA=True)                        # (D, D)
+        H.roof_end('mlp_dw_hid_gemm', ev, 2.0 * M * D * D)
+    else:
+        dW_out, db_out, da2, dW_hid, db_hid = _mlp_out_bwd_unfused(
+            T, M, D, Q, dz, a1, a2, m2, W_t, W_out, csum_epi)
     # d(upper) in upper's dtype: bf16 when the bottom tier hands the MLP a bf16 upper.  A
     # bf16 da1 also gets max |da1| from the GEMM's epilogue (the packed dTab scatter's
     # scale), so the scatter needs no pass of its own over da1

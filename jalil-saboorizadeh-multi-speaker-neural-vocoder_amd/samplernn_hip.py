@@ -110,6 +110,7 @@ _SIGS = {
                               _P, _P],
     'srnn_step_advance': [_P, _I, _P],
     'srnn_nll_logsoftmax_bwd': [_P, _L, _I, _L, _I, _P, _L, _F, _P, _P, _I, _L, _P],
+    'srnn_mlp_out_bwd': [_I, _P, _P, _P, _L, _I, _I, _P, _P, _P, _P, _I, ctypes.POINTER(_I), _P],
 }
 
 
@@ -155,6 +156,7 @@ class _Lib:
                            ('srnn_gemm_amax_taken', []), ('srnn_gemm_csum_taken', []),
                            ('srnn_gemm_logsoftmax_next', []), ('srnn_gemm_logsoftmax_taken', []),
                            ('srnn_blaslt_calls', []), ('srnn_blaslt_set_tune', [_I]),
+                           ('srnn_mlp_out_bwd_ranges', [_I, _L, _I, _I, _I]),
                            ('srnn_blaslt_set_min', [ctypes.c_longlong, ctypes.c_double])):
             fn = getattr(self.dll, name)
             fn.argtypes = args
@@ -206,7 +208,7 @@ def exported_symbols():
                             'srnn_gemm_csum_taken', 'srnn_blaslt_calls', 'srnn_device_share',
                             'srnn_build_hash', 'srnn_dtab_packed_ok', 'srnn_gemm_logsoftmax_next',
                             'srnn_gemm_logsoftmax_taken', 'srnn_blaslt_set_min',
-                            'srnn_blaslt_set_tune']
+                            'srnn_blaslt_set_tune', 'srnn_mlp_out_bwd_ranges']
 
 
 # Callbacks run just before a persistent sweep (gru_xcd / gru_seq) is enqueued.  Such a sweep
@@ -577,6 +579,40 @@ def colsum(x, rows, cols, lds=None, out=None, alpha=1.0, accumulate=False):
     lib().call('srnn_colsum', dcode(x), ptr(x), lds, rows, cols, ptr(out), alpha, int(accumulate),
                ptr(work), work.numel(), stream())
     return out
+
+
+def mlp_out_bwd(dz, a2, wt, ranges=0, want_db=True):
+    """The MLP output layer's backward in one pass over dz (M, Q) and a2 (M, D), bf16, with
+    wt = W_out^T (D, Q): (da2, dW_out, db_out, csp) -- da2 = bf16(dz . W_out) * [a2 > 0],
+    dW_out = dz^T . a2, db_out = colsum(dz) (None unless want_db), csp (M / 128, D) the column
+    sums of da2 per 128-row block (sum its rows for the hidden bias gradient) -- or None when
+    srnn_mlp_out_bwd does not serve the shape (the caller then runs the separate GEMMs).
+    ranges: row ranges (0: the split-K slices of the dz^T . a2 GEMM, whose bits dW_out then
+    keeps, else one workgroup per CU)."""
+    need_cuda(dz, a2, wt)
+    if dz.dtype != torch.bfloat16 or a2.dtype != dz.dtype or wt.dtype != dz.dtype:
+        return None
+    if dz.dim() != 2 or a2.dim() != 2 or wt.dim() != 2 or not (
+            dz.is_contiguous() and a2.is_contiguous() and wt.is_contiguous()):
+        return None
+    M, Q = dz.shape
+    D = a2.shape[1]
+    if a2.shape[0] != M or tuple(wt.shape) != (D, Q):
+        return None
+    R = lib().dll.srnn_mlp_out_bwd_ranges(BF16, M, D, Q, ranges)
+    if R <= 0:
+        return None
+    dev = dz.device
+    da2 = torch.empty((M, D), device=dev, dtype=torch.bfloat16)
+    dW = torch.empty((Q, D), device=dev, dtype=torch.float32)
+    db = torch.empty(Q, device=dev, dtype=torch.float32) if want_db else None
+    csp = torch.empty((M // 128, D), device=dev, dtype=torch.float32)
+    taken = ctypes.c_int(0)
+    lib().call('srnn_mlp_out_bwd', BF16, ptr(dz), ptr(a2), ptr(wt), M, D, Q, ptr(da2), ptr(dW),
+               ptr(db), ptr(csp), R, ctypes.byref(taken), stream())
+    if not taken.value:
+        return None
+    return da2, dW, db, csp
 
 
 def cast(x, dtype):
