@@ -24,6 +24,10 @@ extern "C" {
 #define SRNN_MAX_RNN 4
 
 const char* srnn_last_error(void);
+/* 2.  Version 1 -> 2: srnn_gemm and srnn_gemm_bits gained the SrnnGemmEpilogue* argument in
+ * front of `stream`; the seven entries that armed a max |C| / blocked copy / column sum /
+ * log-softmax request for "the next GEMM" and read back whether one computed it are gone:
+ * that struct carries the requests and the answer.                                       */
 int srnn_abi_version(void);
 /* Content hash (16 hex digits, csrc/srchash.py) of the sources this library was compiled
  * from; the Python binding refuses a library whose hash differs from its tree's (a stale
@@ -55,13 +59,51 @@ int srnn_udequantize2d(const int64_t* k, int64_t ldk, float* out, int rows, int 
  * mask (optional, input dtype, row stride ldmask) zeroes outputs where mask <= 0 (the ReLU
  * backward of model.py:320-321); in a batch, mask's batch stride is strideC, as C's (there
  * is no stride argument of its own), whatever ldmask is.  beta == 0 never reads Cin, even
- * when it is given.  K == 0 gives act(beta * Cin + bias). */
+ * when it is given.  K == 0 gives act(beta * Cin + bias).
+ * epi (optional, NULL = none): further results the same launch may compute, below. */
+
+/* Optional results of one srnn_gemm / srnn_gemm_bits call, computed in the epilogue of the
+ * 256 x 256 gemm3 pair-mode kernels alone.  The call clears `served` on entry and sets the bit
+ * of every request the launched kernel computes; a request whose bit stays clear -- another
+ * backend ran, the shape or epilogue does not fit, the call failed -- left its buffer
+ * untouched, and the caller computes that result with a pass of its own.  Buffers are device
+ * memory, caller-allocated; the struct itself is host memory read and written during the call
+ * only.                                                                                     */
+typedef struct SrnnGemmEpilogue {
+    unsigned* amax;            /* max |C| as float bits, atomicMax into *amax, which must be
+                                * zero beforehand: a bf16-output GEMM (model.py:311-320's da1
+                                * = (da2 W_hid) * relu', the GEMM producing the dTab scatter's
+                                * input).  Requested together with csum, amax alone is served */
+    void* blk;                 /* only with amax: the same GEMM also writes a column-blocked
+                                * copy of its bf16 output, blk[N / 4][M][4] (M x N bf16) -- the
+                                * dTab scatter's operand layout (srnn_mlp_dtab4).  With grouped
+                                * mask bits amax is served without it (AMAX set, BLK clear)  */
+    float* csum;               /* column sums of the stored bf16 output per 128-row block,
+                                * csum[M / 128][N] fp32 (every entry written once, no zeroing
+                                * needed; the caller sums the M / 128 rows): a bf16-output GEMM
+                                * without bit masks (model.py:320's da2 = (dz W_out) * relu',
+                                * whose column sums are the hidden layer's bias gradient,
+                                * model.py:317's Conv1d bias)                                */
+    int logsoftmax;            /* nonzero: C receives log_softmax of every output row
+                                * (model.py:325) instead of the row: logp = (v - max) -
+                                * log(sum exp(v - max)), v = alpha A B^T + bias, the
+                                * logsoftmax_nll arithmetic.  An fp32-output NT GEMM with
+                                * N = 256 (one 256-column tile: whole rows), no mask, no ReLU,
+                                * a per-column bias at most -- the SampleLevelMLP's logits,
+                                * model.py:324                                               */
+    unsigned served;           /* out: SRNN_EPI_* bits of the requests this call computed    */
+} SrnnGemmEpilogue;
+#define SRNN_EPI_AMAX 1u
+#define SRNN_EPI_BLK 2u
+#define SRNN_EPI_CSUM 4u
+#define SRNN_EPI_LOGSOFTMAX 8u
+
 int srnn_gemm(int dtype, int out_dtype, int transA, int transB, int M, int N, int K,
               float alpha, const void* A, int64_t lda, int64_t strideA, const void* B,
               int64_t ldb, int64_t strideB, float beta, const float* Cin, int64_t ldcin,
               int64_t strideCin, void* C, int64_t ldc, int64_t strideC, const float* bias,
               int bias_mode, int relu, int batch, int tile, const void* mask, int64_t ldmask,
-              void* stream);
+              SrnnGemmEpilogue* epi, void* stream);
 
 /* The same product (batch 1) with ReLU masks as bits -- bit c % 16 of the u16 at
  * [row * ld + c / 16] is (value(row, c) > 0): mask_bits (optional) zeroes the outputs whose
@@ -73,7 +115,7 @@ int srnn_gemm_bits(int dtype, int out_dtype, int transA, int transB, int M, int 
                    float beta, const float* Cin, int64_t ldcin, void* C, int64_t ldc,
                    const float* bias, int bias_mode, int relu, int tile,
                    const unsigned short* mask_bits, int64_t ldmb, unsigned short* bits_out,
-                   int64_t ldbo, void* stream);
+                   int64_t ldbo, SrnnGemmEpilogue* epi, void* stream);
 /* bits[row * ldb + c / 16] bit c % 16 = (a[row * lda + c] > 0), a in dtype (M x N).
  * ldb = 0: the grouped layout, u16 [c / 16][row] (N % 64 == 0) -- the same bits, rows
  * contiguous per 16-column group; srnn_gemm_bits takes it (ldmb = 0) and its bf16
@@ -215,38 +257,12 @@ int srnn_mlp_dtab2(int dtype, const void* da, int64_t ldda, const int64_t* x, in
  * columns per 64-bit LDS atomic in 32-bit fixed point at a power-of-2 scale from max |da| *
  * and the most frequent sample value (exact integer sums, deterministic).                 */
 /* srnn_mlp_dtab2 with amax_in (device, may be NULL): max |da| as float bits, measured by  *
- * the GEMM that produced da (srnn_gemm_amax_next), so the packed form skips its own pass  *
+ * the GEMM that produced da (SrnnGemmEpilogue.amax), so the packed form skips its own pass *
  * over da.  Replaces nothing new in the reference: the same model.py:311-320 backward.    */
 int srnn_mlp_dtab3(int dtype, const void* da, int64_t ldda, const int64_t* x, int64_t ldx,
                    int xoff, int B, int Tlen, void* dtab_out, int out_dtype, int D, int FS0, int Q,
                    void* work, size_t work_bytes, float* colsum, int* colsum_done,
                    const unsigned* amax_in, void* stream);
-/* Ask the next bf16-output GEMM that runs on the 256 x 256 gemm3 path (model.py:311-320's
- * da1 = (da2 W_hid) * relu', the GEMM producing the dTab scatter's input) to also write
- * max |C| (float bits, atomicMax into *amax, which must be zero).  srnn_gemm_amax_taken()
- * returns 1 if a GEMM did since (host state; also clears a request no GEMM took).        */
-int srnn_gemm_amax_next(unsigned* amax);
-int srnn_gemm_amax_taken(void);
-/* srnn_gemm_amax_next, and the same GEMM also writes a column-blocked copy of its bf16
- * output into blk[N / 4][M][4] (M x N bf16, caller-allocated); srnn_gemm_amax_taken()
- * then returns 2.  The dTab scatter's operand layout (srnn_mlp_dtab4).                   */
-int srnn_gemm_amax_blk_next(unsigned* amax, void* blk);
-/* Ask the next bf16-output GEMM that runs on the 256 x 256 gemm3 pair path (model.py:320's
- * da2 = (dz W_out) * relu', whose column sums are the hidden layer's bias gradient,
- * model.py:317's Conv1d bias) to also write the column sums of its stored bf16 output per
- * 128-row block into part[M / 128][N] (fp32, caller-allocated; every entry written once, no
- * zeroing needed); the caller sums the M / 128 rows.  srnn_gemm_csum_taken() returns 1 if a
- * GEMM did since (host state; also clears a request no GEMM took).                        */
-int srnn_gemm_csum_next(float* part);
-int srnn_gemm_csum_taken(void);
-/* Ask the next fp32-output NT GEMM with N = 256 (one 256-column tile: whole rows) that runs
- * on the gemm3 pair path -- the SampleLevelMLP's logits, model.py:324 -- to write
- * log_softmax of every output row (model.py:325) instead of the row: logp = (v - max) -
- * log(sum exp(v - max)), v = alpha A B^T + bias, the logsoftmax_nll arithmetic.
- * srnn_gemm_logsoftmax_taken() returns 1 if a GEMM did since (host state; also clears a
- * request no GEMM took).                                                              */
-int srnn_gemm_logsoftmax_next(void);
-int srnn_gemm_logsoftmax_taken(void);
 /* Backward of the SampleLevelMLP's output layer (model.py:320-324) in one pass over dz and
  * a2 (bf16, Q = 256, D % 128 == 0, M % 256 == 0; contiguous rows):
  *   da2[M, D]     = bf16(dz . W_out) * [a2 > 0]  -- wt is W_out^T (D, Q); bit-identical to
@@ -255,7 +271,7 @@ int srnn_gemm_logsoftmax_taken(void);
  *                   deterministic, no atomics)
  *   db[Q]         = column sums of dz, summed the same way (db may be NULL: not computed)
  *   csp[M/128, D] = column sums of the stored da2 per 128-row block, in the order of
- *                   srnn_gemm_csum_next's epilogue (the caller sums the rows: the hidden
+ *                   SrnnGemmEpilogue.csum's epilogue (the caller sums the rows: the hidden
  *                   layer's bias gradient)
  * srnn_mlp_out_bwd_ranges returns R, the row ranges a launch uses, or 0 when the shape is
  * not served.  want > 0: that many, clamped to M / 128.  want = 0: the split-K factor
@@ -268,7 +284,7 @@ int srnn_mlp_out_bwd(int dtype, const void* dz, const void* a2, const void* wt, 
                      int Q, void* da2, float* dW, float* db, float* csp, int R, int* taken,
                      void* stream);
 /* srnn_mlp_dtab3 with blk (device, may be NULL): the column-blocked copy of da
- * (blk[D / 4][B * Tlen][4], srnn_gemm_amax_blk_next) the packed form reads instead of da
+ * (blk[D / 4][B * Tlen][4], SrnnGemmEpilogue.blk) the packed form reads instead of da
  * (whole 128-B lines per load).  Same outputs bit for bit.  A sample histogram skewed past
  * the packed form's precision bound (one value at > 65,536 positions) makes the exact
  * 2^-40 form run instead; a non-finite da makes dTab and colsum NaN.  Replaces

@@ -757,7 +757,7 @@ extern "C" int srnn_mlp_dtab4(int dtype, const void* da, int64_t ldda, const int
         DtabStat* st = (DtabStat*)work;
         SRNN_CHECK_HIP(hipMemsetAsync(st, 0, sizeof(DtabStat), s));
         const int64_t nrows = (int64_t)B * Tlen;
-        // amax_in: max |da| already measured by the GEMM that wrote da (srnn_gemm_amax_next):
+        // amax_in: max |da| already measured by the GEMM that wrote da (SrnnGemmEpilogue.amax):
         // the prep pass only counts the sample values
         const int nb_da = amax_in ? 0 : (int)std::min<int64_t>(1024, std::max<int64_t>(1, nrows / 64));
         const int W = Tlen + 15;

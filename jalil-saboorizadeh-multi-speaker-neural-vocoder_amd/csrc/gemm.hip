@@ -464,11 +464,11 @@ static const GemmRoute kRoutes[] = {
      "gemm: shape not eligible for the thin path"},
     {4, [](const GemmProblem& p, bool forced) { return forced || (p.M <= 512 && g_use_gemm2()); },
      srnn_try_skinny, "gemm: shape not eligible for the skinny path"},
-    // large plain bf16 problems: hipBLASLt (blaslt.cpp) unless a fused epilogue or a pending
+    // large plain bf16 problems: hipBLASLt (blaslt.cpp) unless a fused epilogue or the problem's
     // max |C| / column-sum / log-softmax request needs gemm3; strided batches too (the folded
     // embedding . conv table, 16 x (256 x 1024 x 256) with the embedding shared: 33 us on the
     // 128-tile kernel per step at every batch size)
-    {-1, [](const GemmProblem& p, bool) { return !p.mask && !srnn_gemm_request_pending(); },
+    {-1, [](const GemmProblem& p, bool) { return !p.mask && !p.wants_epilogue(); },
      srnn_try_blaslt, nullptr},
     // large aligned bf16 problems: the 256x256 8-wave kernel (gemm3.hip)
     {5, [](const GemmProblem& p, bool forced) { return p.batch == 1 && (forced || g_use_gemm3()); },
@@ -495,6 +495,7 @@ static int gemm_route(const GemmProblem& p, hipStream_t s) {
 
 int srnn_gemm_run(const GemmProblem& in, hipStream_t s) {
     GemmProblem p = in;
+    if (p.served) *p.served = 0;  // before anything can fail: an erroring call served nothing
     const bool bits = p.mbi || p.mbo;
     if (bits) {
         SRNN_REQUIRE(p.batch == 1 && !(p.mbi && p.mask), "gemm: bit masks need batch 1 and no bf16 mask");
@@ -537,18 +538,27 @@ int srnn_gemm_run(const GemmProblem& in, hipStream_t s) {
     return srnn_relu_bits_impl(p.out_dtype, p.C, p.ldc, p.M, p.N, p.mbo, p.ldmbo, s);
 }
 
+// the caller's optional epilogue requests into the record (null: none)
+static void gemm_requests(GemmProblem& p, SrnnGemmEpilogue* e) {
+    if (!e) return;
+    p.amax = e->amax; p.blk = (bf16*)e->blk; p.csum = e->csum; p.logsoftmax = e->logsoftmax;
+    p.served = &e->served;
+}
+
 extern "C" int srnn_gemm_bits(int dtype, int out_dtype, int transA, int transB, int M, int N,
                               int K, float alpha, const void* A, int64_t lda, const void* B,
                               int64_t ldb, float beta, const float* Cin, int64_t ldcin, void* C,
                               int64_t ldc, const float* bias, int bias_mode, int relu, int tile,
                               const unsigned short* mask_bits, int64_t ldmb,
-                              unsigned short* bits_out, int64_t ldbo, void* stream) {
+                              unsigned short* bits_out, int64_t ldbo, SrnnGemmEpilogue* epi,
+                              void* stream) {
     GemmProblem p;
     p.dtype = dtype; p.out_dtype = out_dtype; p.transA = transA; p.transB = transB;
     p.M = M; p.N = N; p.K = K; p.alpha = alpha; p.beta = beta;
     p.A = A; p.lda = lda; p.B = B; p.ldb = ldb; p.C = C; p.ldc = ldc;
     p.Cin = Cin; p.ldcin = ldcin; p.bias = bias; p.bias_mode = bias_mode; p.relu = relu;
     p.mbi = mask_bits; p.ldmbi = ldmb; p.mbo = bits_out; p.ldmbo = ldbo; p.tile = tile;
+    gemm_requests(p, epi);
     return srnn_gemm_run(p, (hipStream_t)stream);
 }
 
@@ -557,7 +567,7 @@ extern "C" int srnn_gemm(int dtype, int out_dtype, int transA, int transB, int M
                          int64_t ldb, int64_t strideB, float beta, const float* Cin, int64_t ldcin,
                          int64_t strideCin, void* C, int64_t ldc, int64_t strideC,
                          const float* bias, int bias_mode, int relu, int batch, int tile,
-                         const void* mask, int64_t ldmask, void* stream) {
+                         const void* mask, int64_t ldmask, SrnnGemmEpilogue* epi, void* stream) {
     GemmProblem p;
     p.dtype = dtype; p.out_dtype = out_dtype; p.transA = transA; p.transB = transB;
     p.M = M; p.N = N; p.K = K; p.batch = batch; p.alpha = alpha; p.beta = beta;
@@ -565,5 +575,6 @@ extern "C" int srnn_gemm(int dtype, int out_dtype, int transA, int transB, int M
     p.C = C; p.ldc = ldc; p.sC = strideC; p.Cin = Cin; p.ldcin = ldcin; p.sCin = strideCin;
     p.bias = bias; p.bias_mode = bias_mode; p.relu = relu;
     p.mask = mask; p.ldmask = ldmask; p.tile = tile;
+    gemm_requests(p, epi);
     return srnn_gemm_run(p, (hipStream_t)stream);
 }

@@ -1094,85 +1094,31 @@ static int g3_ncu() {
     return ncu;
 }
 
-// One-shot epilogue requests (srnn_gemm_amax_next / _amax_blk_next / _csum_next /
-// _logsoftmax_next).  A request waits for the next gemm3 launch whose kernel variant computes
-// it and is taken there, in launch3, beside the choice of that variant -- so "taken" and "the
-// launched kernel does it" cannot disagree; its *_taken call reports that and clears it.
-struct G3Requests {
-    unsigned* amax = nullptr;  // max |C| of a bf16-output product
-    bf16* blk = nullptr;       // (with amax) also the column-blocked copy of the output
-    float* csum = nullptr;     // column sums of a bf16-output product
-    int lsm = 0;               // row log-softmax of an fp32-output NT product with N = 256
-    int amax_taken = 0, csum_taken = 0, lsm_taken = 0;
-};
-static G3Requests g3_req;
-
-int srnn_gemm_request_pending() { return g3_req.amax || g3_req.csum || g3_req.lsm; }
-
-extern "C" int srnn_gemm_amax_next(unsigned* amax) {
-    g3_req.amax = amax;
-    g3_req.blk = nullptr;
-    g3_req.amax_taken = 0;
-    return 0;
-}
-
-extern "C" int srnn_gemm_amax_blk_next(unsigned* amax, void* blk) {
-    g3_req.amax = amax;
-    g3_req.blk = (bf16*)blk;
-    g3_req.amax_taken = 0;
-    return 0;
-}
-
-extern "C" int srnn_gemm_csum_next(float* part) {
-    g3_req.csum = part;
-    g3_req.csum_taken = 0;
-    return 0;
-}
-
-extern "C" int srnn_gemm_logsoftmax_next(void) {
-    g3_req.lsm = 1;
-    g3_req.lsm_taken = 0;
-    return 0;
-}
-
-extern "C" int srnn_gemm_logsoftmax_taken(void) {
-    const int t = g3_req.lsm_taken;
-    g3_req.lsm = 0;
-    g3_req.lsm_taken = 0;
-    return t;
-}
-
-extern "C" int srnn_gemm_csum_taken(void) {
-    const int t = g3_req.csum_taken;
-    g3_req.csum = nullptr;
-    g3_req.csum_taken = 0;
-    return t;
-}
-
-extern "C" int srnn_gemm_amax_taken(void) {
-    const int t = g3_req.amax_taken;
-    g3_req.amax = nullptr;
-    g3_req.blk = nullptr;
-    g3_req.amax_taken = 0;
-    return t;
-}
-
+// The problem's epilogue requests (GemmProblem::amax / blk / csum / logsoftmax) arrive in g.
+// launch3 serves a request only beside its choice of the kernel variant that computes it, so
+// "served" and "the launched kernel does it" cannot disagree; it nulls every request it does
+// not serve before the launch -- a variant never sees a pointer for a result it does not
+// compute -- and reports the served ones in *served (may be null).
 template <typename TO, bool KCA, bool KCB, bool SW>
-static int launch3(Gemm3Args g, hipStream_t s) {
+static int launch3(Gemm3Args g, unsigned* served, hipStream_t s) {
     constexpr bool BF = sizeof(TO) == 2;
     // pair mode (64-deep stages) when an operand is k-contiguous (full-line DMA pieces) and
     // the k-slice is whole 64-deep stages, the 32-deep 5-slot ring otherwise
     const bool pairable = (KCA || KCB) && (g.K / g.ksplit) % g3p::BK == 0;
     const bool grouped = g.mbi && g.ldmbi == 0;
-    // the pending requests this launch serves: all need a pair-mode kernel's vector epilogue.
+    // the requests as asked; g keeps only those this launch serves
+    const Gemm3Args want = g;
+    g.amax = nullptr; g.blk = nullptr; g.csp = nullptr; g.lsm = 0;
+    unsigned did = 0;
+    // the requests this launch serves: all need a pair-mode kernel's vector epilogue.
     // max |C|: no Cin, no row-major bit masks; column sums: the plain bf16 epilogue only (no
     // Cin, bit masks or max |C|; M % 128 == 0 holds here); log-softmax: one tile column of an
     // NT product, column bias at most, no ReLU
-    const bool amax = BF && SW && g3_req.amax && pairable && g.beta == 0.f &&
+    const bool amax = BF && SW && want.amax && pairable && g.beta == 0.f &&
                       (!g.mbi || grouped) && !g.mbo;
-    const bool csum = BF && SW && g3_req.csum && !amax && pairable && g.beta == 0.f && !g.mbi &&
+    const bool csum = BF && SW && want.csp && !amax && pairable && g.beta == 0.f && !g.mbi &&
                       !g.mbo;
-    const bool lsm = !BF && SW && KCA && KCB && g3_req.lsm && pairable && g.N == g3::BN &&
+    const bool lsm = !BF && SW && KCA && KCB && want.lsm && pairable && g.N == g3::BN &&
                      g.ksplit == 1 && g.beta == 0.f && !g.mask && !g.mbi && !g.mbo &&
                      (!g.bias || g.bias_mode == 1) && !g.relu;
     // the ring ping-pong for the NN shapes with enough tiles for two rounds (A k-contiguous,
@@ -1196,13 +1142,11 @@ static int launch3(Gemm3Args g, hipStream_t s) {
     SRNN_REQUIRE(!grouped || (BF && SW && pair && !g.mbo && g.K / g.ksplit >= 2 * g3p::BK),
                  "gemm3: grouped mask bits need the bf16 pair-mode kernel and >= 2 k-chunks");
     // the blocked copy needs whole 4-column blocks (N % 256 == 0 holds here); the grouped-bits
-    // kernels write none (the caller sees taken == 1 and reads the row-major da1)
+    // kernels write none (the caller sees AMAX without BLK and reads the row-major da1)
     auto take_amax = [&](bool with_blk) {
-        g.amax = g3_req.amax;
-        g.blk = with_blk ? g3_req.blk : nullptr;
-        g3_req.amax = nullptr;
-        g3_req.blk = nullptr;
-        g3_req.amax_taken = g.blk ? 2 : 1;
+        g.amax = want.amax;
+        g.blk = with_blk ? want.blk : nullptr;
+        did |= SRNN_EPI_AMAX | (g.blk ? SRNN_EPI_BLK : 0u);
     };
     if constexpr (BF && SW) {
         if (grouped) {               // grouped bits staged by LDS-DMA (+ max |C| for the dTab)
@@ -1215,13 +1159,12 @@ static int launch3(Gemm3Args g, hipStream_t s) {
             if (amax) take_amax(false);
         } else if (g.mbi || g.mbo) { // row-major ReLU bit masks
             k = pair ? gemm3p_kernel<TO, KCA, KCB, SW, true> : gemm3_kernel<TO, KCA, KCB, SW, true>;
-        } else if (csum) {            // column sums wanted (srnn_gemm_csum_next)
+        } else if (csum) {            // column sums wanted
             k = pf ? gemm3p_kernel<TO, KCA, KCB, SW, 0, true, false, 1>
                    : gemm3p_kernel<TO, KCA, KCB, SW, 0, false, false, 1>;
-            g.csp = g3_req.csum;
-            g3_req.csum = nullptr;
-            g3_req.csum_taken = 1;
-        } else if (amax) {            // max |C| wanted (srnn_gemm_amax_next)
+            g.csp = want.csp;
+            did |= SRNN_EPI_CSUM;
+        } else if (amax) {            // max |C| wanted
             // (SRNN_G3_AMX_PF: with the unit-1 fragment prefetch as well)
             k = env_flag("SRNN_G3_AMX_PF", 0) ? gemm3p_kernel<TO, KCA, KCB, SW, false, true, true>
                                               : gemm3p_kernel<TO, KCA, KCB, SW, false, false, true>;
@@ -1229,11 +1172,10 @@ static int launch3(Gemm3Args g, hipStream_t s) {
         }
     }
     if constexpr (!BF && SW && KCA && KCB) {
-        if (lsm) {                   // row log-softmax in the epilogue (srnn_gemm_logsoftmax_next)
+        if (lsm) {                   // row log-softmax in the epilogue
             k = gemm3p_kernel<TO, KCA, KCB, SW, 0, false, false, 0, 1>;
             g.lsm = 1;
-            g3_req.lsm = 0;
-            g3_req.lsm_taken = 1;
+            did |= SRNN_EPI_LOGSOFTMAX;
         }
     }
     const int lds = pair ? g3p::LDS + (grouped ? 16 * 1024 : g.lsm ? 8 * 1024 : 0) : g3::LDS;
@@ -1242,15 +1184,17 @@ static int launch3(Gemm3Args g, hipStream_t s) {
     dim3 grid(units < ncu ? units : ncu);
     hipLaunchKernelGGL(k, grid, dim3(g3::NT), lds, s, g);
     SRNN_LAUNCH_CHECK();
+    if (served) *served = did;
     return 0;
 }
 
 template <typename TO, bool SW>
-static int launch3_layout(const Gemm3Args& g, bool kca, bool kcb, hipStream_t s) {
-    if (kca && kcb) return launch3<TO, true, true, SW>(g, s);
-    if (kca && !kcb) return launch3<TO, true, false, SW>(g, s);
-    if (!kca && kcb) return launch3<TO, false, true, SW>(g, s);
-    return launch3<TO, false, false, SW>(g, s);
+static int launch3_layout(const Gemm3Args& g, unsigned* served, bool kca, bool kcb,
+                          hipStream_t s) {
+    if (kca && kcb) return launch3<TO, true, true, SW>(g, served, s);
+    if (kca && !kcb) return launch3<TO, true, false, SW>(g, served, s);
+    if (!kca && kcb) return launch3<TO, false, true, SW>(g, served, s);
+    return launch3<TO, false, false, SW>(g, served, s);
 }
 
 // Split-K factor for a plain fp32-out product: the power of two that minimises
@@ -1316,15 +1260,14 @@ int srnn_try_gemm3(const GemmProblem& p, hipStream_t s) {
     g.bias_mode = p.bias_mode; g.relu = p.relu;
     g.diag = env_flag("SRNN_G3DIAG", 0);
     g.mbi = p.mbi; g.ldmbi = p.ldmbi; g.mbo = p.mbo; g.ldmbo = p.ldmbo;
-    g.amax = nullptr;            // the requests: launch3
-    g.blk = nullptr;
-    g.csp = nullptr;
-    g.lsm = 0;
+    // the requests: launch3 keeps those its kernel serves
+    g.amax = p.amax; g.blk = p.blk; g.csp = p.csum; g.lsm = p.logsoftmax;
     g.ksplit = ks;
     g.part = nullptr;
     if (ks == 1)
-        return p.out_dtype == SRNN_F32 ? launch3_layout<float, true>(g, p.kca(), p.kcb(), s)
-                                       : launch3_layout<bf16, true>(g, p.kca(), p.kcb(), s);
+        return p.out_dtype == SRNN_F32
+                   ? launch3_layout<float, true>(g, p.served, p.kca(), p.kcb(), s)
+                   : launch3_layout<bf16, true>(g, p.served, p.kca(), p.kcb(), s);
     if (env_flag("SRNN_G3_SPLITK_PART", 1) && gemm_aligned(p.C, p.ldc, 16, 4)) {
         // partial tiles in a grow-only scratch, then one ordered sum (no memset, no atomics)
         g.part = srnn_splitk_scratch((size_t)ks * M * N * sizeof(float));
@@ -1334,7 +1277,7 @@ int srnn_try_gemm3(const GemmProblem& p, hipStream_t s) {
     } else {
         SRNN_CHECK_HIP(hipMemset2DAsync(p.C, p.ldc * 4, 0, (size_t)N * 4, M, s));
     }
-    const int rc = launch3_layout<float, false>(g, p.kca(), p.kcb(), s);
+    const int rc = launch3_layout<float, false>(g, p.served, p.kca(), p.kcb(), s);
     if (rc || !g.part) return rc;
     return srnn_splitk_sum((const float*)g.part, (float*)p.C, p.ldc, M, N, ks, s);
 }

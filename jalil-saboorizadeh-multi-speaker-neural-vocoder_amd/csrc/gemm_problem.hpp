@@ -3,6 +3,7 @@
 // validated once by srnn_gemm_run, then offered to the backends in the router's order.
 #pragma once
 #include "common.hpp"
+#include "samplernn_hip.h"
 
 struct GemmProblem {
     int dtype = SRNN_F32, out_dtype = SRNN_F32;
@@ -31,11 +32,22 @@ struct GemmProblem {
     unsigned short* mbo = nullptr;
     int64_t ldmbo = 0;
     int tile = -1;  // < 0: the router chooses; else the code that forces one backend (gemm.hip)
+    // optional epilogue requests (SrnnGemmEpilogue, samplernn_hip.h): results only gemm3's
+    // pair-mode kernels compute.  A backend sets a bit of *served (caller-owned, may be null;
+    // srnn_gemm_run clears it on entry) only beside the choice of the kernel variant that
+    // computes that result, so "served" and "the launched kernel does it" cannot disagree;
+    // a request that is not served leaves its buffer untouched and the caller falls back.
+    unsigned* amax = nullptr;  // max |C| of a bf16-output product (the word zero beforehand)
+    bf16* blk = nullptr;       // (with amax) also the column-blocked copy [N / 4][M][4] of C
+    float* csum = nullptr;     // column sums of a bf16-output product per 128-row block
+    int logsoftmax = 0;        // row log-softmax of an fp32-output NT product with N = 256
+    unsigned* served = nullptr;
 
     int es() const { return dtype == SRNN_F32 ? 4 : 2; }      // element size of A, B, mask
     int eo() const { return out_dtype == SRNN_F32 ? 4 : 2; }  // element size of C
     bool kca() const { return !transA; }                      // A is k-contiguous
     bool kcb() const { return transB != 0; }                  // B is k-contiguous
+    bool wants_epilogue() const { return amax || csum || logsoftmax; }
 };
 
 // p on a `bytes` boundary and its leading dimension a multiple of `mult` elements
@@ -54,9 +66,6 @@ int srnn_try_blaslt(const GemmProblem& p, hipStream_t s);   // blaslt.cpp
 int srnn_try_gemm3(const GemmProblem& p, hipStream_t s);    // gemm3.hip (tile 5: whenever eligible)
 int srnn_try_gemm2(const GemmProblem& p, hipStream_t s);    // gemm2.hip
 int srnn_try_general(const GemmProblem& p, hipStream_t s);  // gemm.hip: always takes
-// gemm3.hip: a one-shot epilogue request (srnn_gemm_amax_next, srnn_gemm_csum_next,
-// srnn_gemm_logsoftmax_next) waits for the next gemm3 launch that can serve it
-int srnn_gemm_request_pending();
 
 // f(T{}, TO{}) for the problem's input / output element types
 template <typename F>

@@ -709,10 +709,9 @@ def mlp_forward(mlp, x, upper, ps):
     # tiles hold whole rows), so the (B T, Q) fp32 logits never round-trip through HBM
     # (SRNN_LSM_EPI=0: the separate logsoftmax pass)
     lsm = T == torch.bfloat16 and Q == 256 and os.environ.get('SRNN_LSM_EPI', '1') != '0'
-    if lsm:
-        H.lib().dll.srnn_gemm_logsoftmax_next()
-    z = H.linear(a2, W_out, bias=mlp.output.bias)                    # (B*T, Q) fp32
-    if lsm and H.lib().dll.srnn_gemm_logsoftmax_taken():
+    epi = H.GemmEpilogue(logsoftmax=True) if lsm else None
+    z = H.linear(a2, W_out, bias=mlp.output.bias, epilogue=epi)      # (B*T, Q) fp32
+    if lsm and epi.logsoftmax_served:
         logp = z
         _STATS['lsm_epi'] += 1
     else:
@@ -740,17 +739,17 @@ def _mlp_out_bwd_unfused(T, M, D, Q, dz, a1, a2, m2, W_t, W_out, csum_epi):
     Wo, tB = (W_t[1], True) if W_t is not None else (W_out, False)
     # bf16: the da2 GEMM's epilogue also sums its stored columns per 128-row block (the
     # hidden layer's bias gradient) -- one pass over da2 fewer than a separate column sum
-    csp = None
+    csp = epi = None
     if csum_epi:
         csp = torch.empty((M // 128, D), device=dev, dtype=torch.float32)
-        H.lib().call('srnn_gemm_csum_next', H.ptr(csp))
+        epi = H.GemmEpilogue(csum=csp)
     ev = H.roof_begin()
     if m2 is not None:
-        da2 = H.gemm(dz, Wo, transB=tB, mask_bits=m2, out_dtype=T)
+        da2 = H.gemm(dz, Wo, transB=tB, mask_bits=m2, out_dtype=T, epilogue=epi)
     else:
-        da2 = H.gemm(dz, Wo, transB=tB, mask=a2, out_dtype=T)
+        da2 = H.gemm(dz, Wo, transB=tB, mask=a2, out_dtype=T, epilogue=epi)
     H.roof_end('mlp_da2_gemm', ev, 2.0 * M * D * Q)
-    if csp is not None and not H.lib().dll.srnn_gemm_csum_taken():
+    if csp is not None and not epi.csum_served:
         csp = None
     if csp is not None:
         _STATS['csum_epi'] += 1
@@ -824,27 +823,26 @@ def mlp_backward(ctx, dlogp, nll=None):
     # d(upper) in upper's dtype: bf16 when the bottom tier hands the MLP a bf16 upper.  A
     # bf16 da1 also gets max |da1| from the GEMM's epilogue (the packed dTab scatter's
     # scale), so the scatter needs no pass of its own over da1
-    amax = blk = None
+    amax = blk = epi = None
     if ctx.udt == torch.bfloat16:
         amax = torch.zeros(1, device=dev, dtype=torch.int32)
         if FS0 == 16 and D % 256 == 0 and os.environ.get('SRNN_DTAB_BLK', '0') == '1':
             # ... and a column-blocked copy [D/4][M][4] of da1, the scatter's operand
             blk = torch.empty((D // 4, M, 4), device=dev, dtype=torch.bfloat16)
-            H.lib().call('srnn_gemm_amax_blk_next', H.ptr(amax), H.ptr(blk))
-        else:
-            H.lib().call('srnn_gemm_amax_next', H.ptr(amax))
+        epi = H.GemmEpilogue(amax=amax, blk=blk)
     Wh, tB = (W_t[0], True) if W_t is not None else (W_hid, False)
     ev = H.roof_begin()
     if m1 is not None:
-        da1 = H.gemm(da2, Wh, transB=tB, mask_bits=m1, out_dtype=ctx.udt)     # (M, D)
+        da1 = H.gemm(da2, Wh, transB=tB, mask_bits=m1, out_dtype=ctx.udt,     # (M, D)
+                     epilogue=epi)
     else:
-        da1 = H.gemm(da2, Wh, transB=tB, mask=a1, out_dtype=ctx.udt)          # (M, D)
+        da1 = H.gemm(da2, Wh, transB=tB, mask=a1, out_dtype=ctx.udt,          # (M, D)
+                     epilogue=epi)
     H.roof_end('mlp_da1_gemm', ev, 2.0 * M * D * D)
-    if amax is not None:
-        taken = H.lib().dll.srnn_gemm_amax_taken()
-        if taken != 2:
+    if epi is not None:
+        if not epi.blk_served:
             blk = None
-        if not taken:
+        if not epi.amax_served:
             amax = None
     # folded embedding . conv backward: dTab[q][k][:] += da1[t] for x_{t+k} = q
     dtabT = torch.empty((Q, FS0 * D), device=dev, dtype=T)

@@ -37,9 +37,9 @@ _SIGS = {
     'srnn_uquantize_f32_host': [_P, _P, _L, _I],
     'srnn_udequantize_host': [_P, _P, _L, _I],
     'srnn_gemm': [_I, _I, _I, _I, _I, _I, _I, _F, _P, _L, _L, _P, _L, _L, _F, _P, _L, _L, _P, _L,
-                  _L, _P, _I, _I, _I, _I, _P, _L, _P],
+                  _L, _P, _I, _I, _I, _I, _P, _L, _P, _P],
     'srnn_gemm_bits': [_I, _I, _I, _I, _I, _I, _I, _F, _P, _L, _P, _L, _F, _P, _L, _P, _L, _P, _I,
-                       _I, _I, _P, _L, _P, _L, _P],
+                       _I, _I, _P, _L, _P, _L, _P, _P],
     'srnn_relu_bits': [_I, _P, _L, _I, _I, _P, _L, _P],
     'srnn_mlp_l1_bits': [_P, _P, _L, _I, _I, _I, _P, _L, _P, _L, _I, _I, _I, _P, _L, _P],
     'srnn_gru_cell': [_I, _I, _I, _I, _P, _L, _P, _P, _P, _L, _P, _L, _P, _L, _P, _P, _P, _L, _P,
@@ -54,10 +54,7 @@ _SIGS = {
                        ctypes.POINTER(_I), _P, _P],
     'srnn_mlp_dtab4': [_I, _P, _L, _P, _L, _I, _I, _I, _P, _I, _I, _I, _I, _P, _SZ, _P,
                        ctypes.POINTER(_I), _P, _P, _P],
-    'srnn_gemm_amax_next': [_P],
     'srnn_cast_multi': [_I, _P, _P, _P, _P],
-    'srnn_gemm_amax_blk_next': [_P, _P],
-    'srnn_gemm_csum_next': [_P],
     'srnn_logsoftmax_nll': [_P, _L, _P, _L, _I, _L, _I, _P, _P, _L, _P, _I, _L, _F, _P],
     'srnn_logsoftmax_bwd': [_P, _L, _P, _L, _L, _I, _P, _I, _L, _P],
     'srnn_nll_fwd': [_P, _L, _P, _L, _I, _L, _P, _P],
@@ -128,6 +125,29 @@ class SrnnModel(ctypes.Structure):
                 ('tab', _P), ('w_hid', _P), ('b_hid', _P), ('w_out', _P), ('b_out', _P)]
 
 
+EPI_AMAX, EPI_BLK, EPI_CSUM, EPI_LOGSOFTMAX = 1, 2, 4, 8
+
+
+class GemmEpilogue(ctypes.Structure):
+    """The C ABI's SrnnGemmEpilogue: optional results of one gemm() call that only gemm3's
+    pair-mode kernels compute -- amax (1-element int32 tensor, zero beforehand: max |C| as
+    float bits), blk (with amax: the (N / 4, M, 4) column-blocked copy of a bf16 C), csum
+    ((M / 128, N) fp32 column sums per 128-row block), logsoftmax (C receives its rows'
+    log-softmax).  After the call `served` has the EPI_* bit of every request the launched
+    kernel computed; an unserved request left its buffer untouched.  The tensors must outlive
+    the call (the struct holds plain pointers)."""
+    _fields_ = [('amax', _P), ('blk', _P), ('csum', _P), ('logsoftmax', _I),
+                ('served', ctypes.c_uint)]
+
+    def __init__(self, amax=None, blk=None, csum=None, logsoftmax=False):
+        super().__init__(ptr(amax), ptr(blk), ptr(csum), int(logsoftmax), 0)
+
+    amax_served = property(lambda self: bool(self.served & EPI_AMAX))
+    blk_served = property(lambda self: bool(self.served & EPI_BLK))
+    csum_served = property(lambda self: bool(self.served & EPI_CSUM))
+    logsoftmax_served = property(lambda self: bool(self.served & EPI_LOGSOFTMAX))
+
+
 class _Lib:
     def __init__(self, path):
         if not os.path.exists(path):
@@ -153,8 +173,6 @@ class _Lib:
         # query entry points called on .dll directly (pointers are passed as plain ints, so
         # every pointer argument needs its declared type)
         for name, args in (('srnn_gru_xcd_error', [_P]), ('srnn_persistent_error_take', []),
-                           ('srnn_gemm_amax_taken', []), ('srnn_gemm_csum_taken', []),
-                           ('srnn_gemm_logsoftmax_next', []), ('srnn_gemm_logsoftmax_taken', []),
                            ('srnn_blaslt_calls', []), ('srnn_blaslt_set_tune', [_I]),
                            ('srnn_mlp_out_bwd_ranges', [_I, _L, _I, _I, _I]),
                            ('srnn_blaslt_set_min', [ctypes.c_longlong, ctypes.c_double])):
@@ -204,11 +222,10 @@ def exported_symbols():
                             'srnn_gen_persistent_rows_level',
                             'srnn_gru_xcd_work_bytes',
                             'srnn_gru_xcd_bwd_work_bytes', 'srnn_gru_xcd_error',
-                            'srnn_persistent_error_take', 'srnn_gemm_amax_taken',
-                            'srnn_gemm_csum_taken', 'srnn_blaslt_calls', 'srnn_device_share',
-                            'srnn_build_hash', 'srnn_dtab_packed_ok', 'srnn_gemm_logsoftmax_next',
-                            'srnn_gemm_logsoftmax_taken', 'srnn_blaslt_set_min',
-                            'srnn_blaslt_set_tune', 'srnn_mlp_out_bwd_ranges']
+                            'srnn_persistent_error_take', 'srnn_blaslt_calls',
+                            'srnn_device_share', 'srnn_build_hash', 'srnn_dtab_packed_ok',
+                            'srnn_blaslt_set_min', 'srnn_blaslt_set_tune',
+                            'srnn_mlp_out_bwd_ranges']
 
 
 # Callbacks run just before a persistent sweep (gru_xcd / gru_seq) is enqueued.  Such a sweep
@@ -508,10 +525,11 @@ def bits_ld(bits):
 def gemm(a, b, transA=False, transB=False, out=None, out_dtype=torch.float32, bias=None,
          bias_mode=1, relu=False, alpha=1.0, beta=0.0, cin=None, mask=None, M=None, N=None, K=None,
          lda=None, ldb=None, ldc=None, ldcin=None, batch=1, sA=0, sB=0, sC=0, sCin=0, tile=-1,
-         mask_bits=None, bits_out=None):
+         mask_bits=None, bits_out=None, epilogue=None):
     """C = act(alpha op(A) op(B) + beta Cin + bias) on row-major 2-D views (or strided batches).
     mask_bits / bits_out: the ReLU mask as bits (relu_bits buffers), read in place of `mask` /
-    written for C (batch 1).
+    written for C (batch 1).  epilogue: a GemmEpilogue of further results wanted from the same
+    launch; read its `served` afterwards.
     mask: row stride mask.stride(0); in a batch its batch stride is sC, as the output's (so a
     batched mask is laid out as `out` is, rows apart by its own stride).  beta == 0 never reads
     cin; K == 0 gives act(beta cin + bias).  tile >= 3 forces one backend and raises ("not
@@ -537,6 +555,7 @@ def gemm(a, b, transA=False, transB=False, out=None, out_dtype=torch.float32, bi
     if _GEMM_LOG:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
+    epi = ctypes.byref(epilogue) if epilogue is not None else None
     if mask_bits is not None or bits_out is not None:
         if batch != 1 or mask is not None:
             raise ValueError('gemm: bit masks need batch 1 and no tensor mask')
@@ -544,28 +563,29 @@ def gemm(a, b, transA=False, transB=False, out=None, out_dtype=torch.float32, bi
                    alpha, ptr(a), lda, ptr(b), ldb, beta, ptr(cin), ldcin or 0, ptr(out), ldc,
                    ptr(bias), bias_mode, int(relu), tile, ptr(mask_bits),
                    bits_ld(mask_bits) if mask_bits is not None else 0, ptr(bits_out),
-                   bits_ld(bits_out) if bits_out is not None else 0, stream())
+                   bits_ld(bits_out) if bits_out is not None else 0, epi, stream())
     else:
         lib().call('srnn_gemm', dcode(a), dcode(out), int(transA), int(transB), M, N, K, alpha,
                    ptr(a), lda, sA, ptr(b), ldb, sB, beta, ptr(cin), ldcin or 0, sCin, ptr(out),
                    ldc, sC, ptr(bias), bias_mode, int(relu), batch, tile, ptr(mask),
-                   (mask.stride(0) if mask is not None else 0), stream())
+                   (mask.stride(0) if mask is not None else 0), epi, stream())
     if _GEMM_LOG:
         torch.cuda.synchronize()
         us = (time.perf_counter() - t0) * 1e6
         sys.stderr.write('gemm M=%d N=%d K=%d batch=%d tA=%d tB=%d %s->%s mask=%d bias=%d relu=%d '
-                         'cin=%d %.1f us %.1f TF/s\n' % (
+                         'cin=%d epi=%d %.1f us %.1f TF/s\n' % (
                              M, N, K, batch, transA, transB, a.dtype, out.dtype, mask is not None,
-                             bias is not None, relu, cin is not None, us,
+                             bias is not None, relu, cin is not None,
+                             epilogue.served if epilogue is not None else 0, us,
                              2.0 * M * N * K * batch / us / 1e6))
     return out
 
 
 def linear(x, w, bias=None, relu=False, out_dtype=torch.float32, out=None, cin=None, beta=0.0,
-           bits_out=None):
+           bits_out=None, epilogue=None):
     """y = act(x . w^T + bias (+ beta * cin)) for 2-D x (M, K) and w (N, K)."""
     return gemm(x, w, transB=True, bias=bias, relu=relu, out_dtype=out_dtype, out=out, cin=cin,
-                beta=beta, bits_out=bits_out)
+                beta=beta, bits_out=bits_out, epilogue=epilogue)
 
 
 def colsum(x, rows, cols, lds=None, out=None, alpha=1.0, accumulate=False):

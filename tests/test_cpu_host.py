@@ -26,7 +26,7 @@ def test_library_exports_every_header_symbol():
     for s in syms:
         assert hasattr(lib.dll, s), s
     assert set(syms) <= set(H.exported_symbols())
-    assert lib.dll.srnn_abi_version() == 1
+    assert lib.dll.srnn_abi_version() == 2
 
 
 def test_library_build_hash_matches_tree():

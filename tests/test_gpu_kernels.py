@@ -932,7 +932,7 @@ def test_mlp_dtab_blocked_operand_bit_identical(hip, B, Tl):
 
 
 def test_gemm_writes_blocked_copy(hip):
-    """srnn_gemm_amax_blk_next: the ReLU-masked bf16 GEMM producing da1 also writes its output
+    """GemmEpilogue(amax, blk): the ReLU-masked bf16 GEMM producing da1 also writes its output
     column-blocked ([N/4][M][4]) and max |C|; the copy is the output, permuted, bit for bit
     (the da1 GEMM's shape class: M = B T rows, a 256-tile grid that fills the chip)."""
     M, N, K = 65536, 1024, 512
@@ -942,11 +942,10 @@ def test_gemm_writes_blocked_copy(hip):
     mask = torch.randn(M, N, generator=g).to(DEV, torch.bfloat16)
     amax = torch.zeros(1, device=DEV, dtype=torch.int32)
     blk = torch.full((N // 4, M, 4), float('nan'), device=DEV, dtype=torch.bfloat16)
-    hip.lib().call('srnn_gemm_amax_blk_next', hip.ptr(amax), hip.ptr(blk))
-    C = hip.gemm(A, W, transB=True, mask=mask, out_dtype=torch.bfloat16)
-    taken = hip.lib().dll.srnn_gemm_amax_taken()
+    epi = hip.GemmEpilogue(amax=amax, blk=blk)
+    C = hip.gemm(A, W, transB=True, mask=mask, out_dtype=torch.bfloat16, epilogue=epi)
     torch.cuda.synchronize()
-    assert taken == 2
+    assert epi.served == hip.EPI_AMAX | hip.EPI_BLK
     ref = C.reshape(M, N // 4, 4).permute(1, 0, 2)
     assert torch.equal(blk.view(torch.int16), ref.contiguous().view(torch.int16))
     assert amax.view(torch.float32).item() == C.float().abs().max().item()
@@ -1484,10 +1483,9 @@ def test_gemm_mask_bits_grouped(hip, M, N, K, amax):
     res = []
     for kw in (dict(mask=act), dict(mask_bits=bits)):
         mx = torch.zeros(1, device=DEV, dtype=torch.int32)
-        if amax:
-            hip.lib().call('srnn_gemm_amax_next', hip.ptr(mx))
-        o = hip.gemm(A, W, transB=True, out_dtype=bf, **kw)
-        taken = hip.lib().dll.srnn_gemm_amax_taken() if amax else 0
+        epi = hip.GemmEpilogue(amax=mx) if amax else None
+        o = hip.gemm(A, W, transB=True, out_dtype=bf, epilogue=epi, **kw)
+        taken = epi.served if amax else 0
         torch.cuda.synchronize()
         res.append((o, int(mx.item()), taken))
     assert torch.equal(res[0][0], res[1][0])
@@ -1497,7 +1495,7 @@ def test_gemm_mask_bits_grouped(hip, M, N, K, amax):
         ref = res[0][0].float().abs().max().item()
         assert res[1][1] == int(np.float32(ref).view(np.int32))
     if M * N >= 32768 * 1024 and K >= 128:
-        assert res[1][2] == 1 or not amax                   # the LDS-staged kernel took it
+        assert res[1][2] == hip.EPI_AMAX or not amax        # the LDS-staged kernel served it
     o3 = hip.gemm(A, W, transB=True, mask_bits=bits)       # fp32 out: the expanded fallback
     o4 = hip.gemm(A, W, transB=True, mask=act)
     assert torch.equal(o3, o4)
@@ -1572,36 +1570,36 @@ def test_fused_nll_logsoftmax_backward_bit_identical(hip, monkeypatch, dtype):
 
 
 def test_gemm_amax_request(hip):
-    """srnn_gemm_amax_next: the next bf16-output GEMM on the gemm3 path also writes max |C|
+    """GemmEpilogue(amax): a bf16-output GEMM on the gemm3 path also writes max |C|
     (as float bits) -- exactly the max of the bf16 values it stored; a GEMM that takes another
-    path leaves the request untaken."""
+    path leaves the request unserved."""
     g = torch.Generator().manual_seed(11)
     a = (torch.randn(8192, 1024, generator=g)).to(DEV, torch.bfloat16)
     w = (torch.randn(1024, 1024, generator=g) * 0.05).to(DEV, torch.bfloat16)
     mask = (torch.rand(8192, 1024, generator=g) > 0.5).to(DEV, torch.bfloat16)
     amax = torch.zeros(1, device=DEV, dtype=torch.int32)
-    hip.lib().call('srnn_gemm_amax_next', hip.ptr(amax))
-    c = hip.gemm(a, w, mask=mask, out_dtype=torch.bfloat16)
-    assert hip.lib().dll.srnn_gemm_amax_taken() == 1
+    epi = hip.GemmEpilogue(amax=amax)
+    c = hip.gemm(a, w, mask=mask, out_dtype=torch.bfloat16, epilogue=epi)
+    assert epi.served == hip.EPI_AMAX
     torch.cuda.synchronize()
     got = amax.view(torch.float32).item()
     assert got == c.float().abs().max().item()
-    # a small GEMM (not on the 256 x 256 path) does not take the request
+    # a small GEMM (not on the 256 x 256 path) does not serve the request
     amax.zero_()
-    hip.lib().call('srnn_gemm_amax_next', hip.ptr(amax))
-    hip.gemm(a[:64, :64].contiguous(), w[:64, :64].contiguous(), out_dtype=torch.bfloat16)
-    assert hip.lib().dll.srnn_gemm_amax_taken() == 0
+    hip.gemm(a[:64, :64].contiguous(), w[:64, :64].contiguous(), out_dtype=torch.bfloat16,
+             epilogue=epi)
+    assert epi.served == 0
 
 
 @pytest.mark.parametrize('form', ['nt_mask', 'nn_plain', 'nt_bias_relu'])
 def test_gemm_csum_request(hip, form):
-    """srnn_gemm_csum_next: the next bf16-output GEMM on the gemm3 pair path also writes the
+    """GemmEpilogue(csum): a bf16-output GEMM on the gemm3 pair path also writes the
     column sums of the bf16 values it stored, per 128-row block (part[M / 128][N]): each block
     row equals the fp64 sum of those stored values within fp32 rounding (128 terms), and the
     product itself is bit-identical to the same GEMM without the request.  nt_mask is the
     MLP's da2 = (dz W_out^T) * relu' form (model.py:320); nn_plain a shape that otherwise takes
     the ring ping-pong (the request keeps it on the pair kernel).  A bit-mask GEMM and a
-    small GEMM leave the request untaken."""
+    small GEMM leave the request unserved and its buffer as it was."""
     g = torch.Generator().manual_seed(12)
     M, N, K = (8192, 1024, 256) if form != 'nn_plain' else (8192, 4096, 512)
     a = torch.randn(M, K, generator=g).to(DEV, torch.bfloat16)
@@ -1617,9 +1615,9 @@ def test_gemm_csum_request(hip, form):
         kw.update(bias=torch.randn(N, generator=g).to(DEV), relu=True)
     plain = hip.gemm(a, w, **kw)
     part = torch.full((M // 128, N), float('nan'), device=DEV)
-    hip.lib().call('srnn_gemm_csum_next', hip.ptr(part))
-    c = hip.gemm(a, w, **kw)
-    assert hip.lib().dll.srnn_gemm_csum_taken() == 1
+    epi = hip.GemmEpilogue(csum=part)
+    c = hip.gemm(a, w, epilogue=epi, **kw)
+    assert epi.served == hip.EPI_CSUM
     torch.cuda.synchronize()
     assert torch.equal(c, plain)
     ref = c.double().reshape(M // 128, 128, N).sum(1)
@@ -1627,14 +1625,16 @@ def test_gemm_csum_request(hip, form):
     err = (part.double() - ref).abs()
     assert torch.isfinite(part).all()
     assert (err <= 128 * 2.0 ** -24 * mag + 1e-30).all(), float((err / (mag + 1e-30)).max())
-    # bit masks (their own kernels) and a small GEMM do not take the request
+    # bit masks (their own kernels) and a small GEMM do not serve the request
     bits = torch.zeros((M, N // 16), device=DEV, dtype=torch.int16)
-    hip.lib().call('srnn_gemm_csum_next', hip.ptr(part))
-    hip.gemm(a, w, mask_bits=bits, **{k: v for k, v in kw.items() if k != 'mask'})
-    assert hip.lib().dll.srnn_gemm_csum_taken() == 0
-    hip.lib().call('srnn_gemm_csum_next', hip.ptr(part))
-    hip.gemm(a[:64, :64].contiguous(), a[:64, :64].contiguous(), out_dtype=torch.bfloat16)
-    assert hip.lib().dll.srnn_gemm_csum_taken() == 0
+    part0 = part.clone()
+    hip.gemm(a, w, mask_bits=bits, epilogue=epi, **{k: v for k, v in kw.items() if k != 'mask'})
+    assert epi.served == 0
+    epi.served = hip.EPI_CSUM                                 # the call clears it
+    hip.gemm(a[:64, :64].contiguous(), a[:64, :64].contiguous(), out_dtype=torch.bfloat16,
+             epilogue=epi)
+    assert epi.served == 0
+    assert torch.equal(part, part0)
 
 
 @pytest.mark.parametrize('S,n', [(6, 512), (5, 5000)])
@@ -1739,11 +1739,11 @@ def test_cast_dense_and_strided(hip, src_dt, dst_dt, rows, cols):
         assert bool((dst[:, :2] == -1).all()) and bool((dst[:, cols + 1:] == -1).all())
 
 
-# ---- gemm3's one-shot log-softmax epilogue request (srnn_gemm_logsoftmax_next)
+# ---- gemm3's log-softmax epilogue request (GemmEpilogue(logsoftmax=True))
 
 @pytest.mark.parametrize('M', [32768, 131072])
 def test_logits_gemm_logsoftmax_epilogue(hip, M):
-    """srnn_gemm_logsoftmax_next: the logits GEMM (bf16 a2 (M, 1024) . W_out^T (256, 1024) +
+    """GemmEpilogue(logsoftmax=True): the logits GEMM (bf16 a2 (M, 1024) . W_out^T (256, 1024) +
     bias, fp32 out) writes log_softmax of its rows (model.py:324-325) -- against torch's
     log_softmax of the fp32 product and against the unfused path (fp32 logits, then
     srnn_logsoftmax_nll); several tiles per workgroup at M = 131072."""
@@ -1751,12 +1751,10 @@ def test_logits_gemm_logsoftmax_epilogue(hip, M):
     a = (_rand(M, 1024, seed=7) * 2).to(DEV, bf)
     w = (_rand(256, 1024, seed=8) * 0.2).to(DEV, bf)
     b = _rand(256, seed=9).to(DEV)
-    lib = hip.lib().dll
-    lib.srnn_gemm_logsoftmax_next()
-    lp = hip.linear(a, w, bias=b)
-    assert lib.srnn_gemm_logsoftmax_taken() == 1
+    epi = hip.GemmEpilogue(logsoftmax=True)
+    lp = hip.linear(a, w, bias=b, epilogue=epi)
+    assert epi.served == hip.EPI_LOGSOFTMAX
     z = hip.linear(a, w, bias=b)                              # plain logits (no request)
-    assert lib.srnn_gemm_logsoftmax_taken() == 0
     lp2 = torch.empty_like(z)
     hip.lib().call('srnn_logsoftmax_nll', hip.ptr(z), 256, None, 0, M, M, 256, None,
                    hip.ptr(lp2), 256, None, hip.F32, 0, 0.0, hip.stream())
@@ -1770,35 +1768,193 @@ def test_logits_gemm_logsoftmax_epilogue(hip, M):
 @pytest.mark.parametrize('M', [300, 4096])
 def test_logsoftmax_request_not_taken_falls_back(hip, M):
     """Shapes the epilogue does not take (M not a multiple of 256; too few 256-row tiles for
-    the gemm3 path): the request is not taken, the GEMM writes plain logits, and taken()
-    clears the request."""
+    the gemm3 path): the request is not served and the GEMM writes plain logits."""
     bf = torch.bfloat16
     a = _rand(M, 1024, seed=10).to(DEV, bf)
     w = _rand(256, 1024, seed=11).to(DEV, bf)
-    lib = hip.lib().dll
-    lib.srnn_gemm_logsoftmax_next()
-    z = hip.linear(a, w)
-    assert lib.srnn_gemm_logsoftmax_taken() == 0
+    epi = hip.GemmEpilogue(logsoftmax=True)
+    z = hip.linear(a, w, epilogue=epi)
+    assert epi.served == 0
     torch.cuda.synchronize()
     ref = a.float() @ w.float().t()
     torch.testing.assert_close(z, ref, atol=2e-3 * 32, rtol=1e-2)
 
 
 def test_logsoftmax_request_not_taken_with_relu(hip):
-    """The log-softmax epilogue has no ReLU: a request ahead of a ReLU GEMM is not taken and
+    """The log-softmax epilogue has no ReLU: a request on a ReLU GEMM is not served and
     leaves the output as it is without a request.  24576 x 256 x 128 with a bias: 96 row tiles,
     the fewest gemm3 takes unforced at N = 256."""
     bf = torch.bfloat16
     a = _rand(24576, 128, seed=12).to(DEV, bf)
     w = _rand(256, 128, seed=13).to(DEV, bf)
     b = _rand(256, seed=14).to(DEV)
-    lib = hip.lib().dll
-    lib.srnn_gemm_logsoftmax_next()
-    hip.linear(a, w, bias=b, relu=False)
-    assert lib.srnn_gemm_logsoftmax_taken() == 1
-    lib.srnn_gemm_logsoftmax_next()
-    z = hip.linear(a, w, bias=b, relu=True)
-    assert lib.srnn_gemm_logsoftmax_taken() == 0
+    epi = hip.GemmEpilogue(logsoftmax=True)
+    hip.linear(a, w, bias=b, relu=False, epilogue=epi)
+    assert epi.served == hip.EPI_LOGSOFTMAX
+    z = hip.linear(a, w, bias=b, relu=True, epilogue=epi)
+    assert epi.served == 0
     z0 = hip.linear(a, w, bias=b, relu=True)                  # no request
     torch.cuda.synchronize()
     assert torch.equal(z, z0)
+
+
+# ---- epilogue requests travel with their GEMM (GemmEpilogue): nothing stays armed
+
+_EPI_WORD = 0x7FC0BEEF          # a recognisable non-zero word (a NaN as float bits)
+
+
+@pytest.fixture(scope='module')
+def epi_ops(hip):
+    """bf16 NT operands of the smallest gemm3 shapes (M = 512 and its first 256 rows, N = 256,
+    K = 128) and their plain tile-5 products, computed before any request exists."""
+    bf = torch.bfloat16
+    a = _rand(512, 128, seed=31).to(DEV, bf)
+    w = _rand(256, 128, seed=32).to(DEV, bf)
+    plain = {M: hip.gemm(a[:M], w, transB=True, out_dtype=bf, tile=5) for M in (256, 512)}
+    torch.cuda.synchronize()
+    return a, w, plain
+
+
+def _epi_canaries(M, N):
+    """(amax, blk, csum) request buffers of an M x N product, canary-filled, and their bits."""
+    amax = torch.full((1,), _EPI_WORD, device=DEV, dtype=torch.int32)
+    blk = torch.full((N // 4, M, 4), float('nan'), device=DEV, dtype=torch.bfloat16)
+    csum = torch.full((M // 128, N), float('nan'), device=DEV)
+    return (amax, blk, csum), [_epi_bits(t).clone() for t in (amax, blk, csum)]
+
+
+def _epi_bits(t):
+    return t.view(torch.int16) if t.dtype == torch.bfloat16 else t.view(torch.int32)
+
+
+def test_gemm_epilogue_failed_call_leaves_nothing_armed(hip, epi_ops):
+    """A GEMM that raises with requests attached (tile 6 refuses 256 x 256 x 128) reports
+    nothing served and writes none of the buffers, and the same product afterwards, without
+    requests, is the plain product: no request outlives its call."""
+    a, w, plain = epi_ops
+    bufs, before = _epi_canaries(256, 256)
+    epi = hip.GemmEpilogue(amax=bufs[0], blk=bufs[1], csum=bufs[2])
+    epi.served = 0xF
+    with pytest.raises(RuntimeError, match='not eligible'):
+        hip.gemm(a[:256], w, transB=True, out_dtype=torch.bfloat16, tile=6, epilogue=epi)
+    assert epi.served == 0
+    c = hip.gemm(a[:256], w, transB=True, out_dtype=torch.bfloat16, tile=5)
+    torch.cuda.synchronize()
+    for t, b in zip(bufs, before):
+        assert torch.equal(_epi_bits(t), b)
+    assert torch.equal(c, plain[256])
+
+
+@pytest.mark.parametrize('case', ['small_bf16', 'fp32_in'])
+def test_gemm_epilogue_unserved_means_untouched(hip, epi_ops, case):
+    """Requests on a call the router sends to another backend (64 x 64 x 64 unforced; an
+    fp32-input product): served == 0, the buffers keep their canaries and the output is the
+    output of the call without requests."""
+    a, w, _ = epi_ops
+    if case == 'small_bf16':
+        x, y, kw = a[:64, :64].contiguous(), w[:64, :64].contiguous(), \
+            dict(out_dtype=torch.bfloat16)
+    else:
+        x, y, kw = a[:256].float(), w.float(), {}
+    bufs, before = _epi_canaries(256, 256)
+    epi = hip.GemmEpilogue(amax=bufs[0], blk=bufs[1], csum=bufs[2], logsoftmax=True)
+    epi.served = 0xF
+    c = hip.gemm(x, y, transB=True, epilogue=epi, **kw)
+    c0 = hip.gemm(x, y, transB=True, **kw)
+    torch.cuda.synchronize()
+    assert epi.served == 0
+    for t, b in zip(bufs, before):
+        assert torch.equal(_epi_bits(t), b)
+    assert torch.equal(c, c0)
+
+
+@pytest.mark.parametrize('with_blk', [False, True])
+def test_gemm_epilogue_amax_wins_over_csum(hip, epi_ops, with_blk):
+    """max |C| and column sums asked of one 512 x 256 x 128 product: the max (and the blocked
+    copy when given) is served, the column sums are not and their buffer is untouched; the
+    max is exact and C is the plain product."""
+    a, w, plain = epi_ops
+    (_, blk, csum), (_, _, csum0) = _epi_canaries(512, 256)
+    amax = torch.zeros(1, device=DEV, dtype=torch.int32)
+    epi = hip.GemmEpilogue(amax=amax, blk=blk if with_blk else None, csum=csum)
+    c = hip.gemm(a, w, transB=True, out_dtype=torch.bfloat16, tile=5, epilogue=epi)
+    torch.cuda.synchronize()
+    assert epi.served == hip.EPI_AMAX | (hip.EPI_BLK if with_blk else 0)
+    assert epi.amax_served and epi.blk_served == with_blk and not epi.csum_served
+    assert torch.equal(_epi_bits(csum), csum0)
+    assert amax.view(torch.float32).item() == c.float().abs().max().item()
+    assert torch.equal(c, plain[512])
+    if with_blk:
+        ref = c.reshape(512, 64, 4).permute(1, 0, 2).contiguous()
+        assert torch.equal(_epi_bits(blk), _epi_bits(ref))
+
+
+@pytest.mark.parametrize('req', ['amax_blk', 'csum', 'logsoftmax'])
+def test_gemm_epilogue_each_request_alone(hip, epi_ops, req):
+    """Each request alone on 256 x 256 x 128 (one tile, tile 5): max |C| with the blocked copy
+    (the permuted C bit for bit), the column sums per 128-row block (fp64 sums of the stored C
+    within 128 fp32 roundings), the row log-softmax of the fp32 logits with a column bias
+    (torch's log_softmax of the fp64 product, 5e-5)."""
+    a, w, plain = epi_ops
+    a = a[:256]
+    bf = torch.bfloat16
+    (_, blk, csum), _ = _epi_canaries(256, 256)
+    if req == 'amax_blk':
+        amax = torch.zeros(1, device=DEV, dtype=torch.int32)
+        epi = hip.GemmEpilogue(amax=amax, blk=blk)
+        c = hip.gemm(a, w, transB=True, out_dtype=bf, tile=5, epilogue=epi)
+        torch.cuda.synchronize()
+        assert epi.served == hip.EPI_AMAX | hip.EPI_BLK
+        assert torch.equal(c, plain[256])
+        ref = c.reshape(256, 64, 4).permute(1, 0, 2).contiguous()
+        assert torch.equal(_epi_bits(blk), _epi_bits(ref))
+        assert amax.view(torch.float32).item() == c.float().abs().max().item()
+    elif req == 'csum':
+        epi = hip.GemmEpilogue(csum=csum)
+        c = hip.gemm(a, w, transB=True, out_dtype=bf, tile=5, epilogue=epi)
+        torch.cuda.synchronize()
+        assert epi.served == hip.EPI_CSUM
+        assert torch.equal(c, plain[256])
+        ref = c.double().reshape(2, 128, 256).sum(1)
+        mag = c.double().abs().reshape(2, 128, 256).sum(1)
+        err = (csum.double() - ref).abs()
+        assert torch.isfinite(csum).all()
+        assert (err <= 128 * 2.0 ** -24 * mag + 1e-30).all(), float((err / (mag + 1e-30)).max())
+    else:
+        b = _rand(256, seed=33).to(DEV)
+        epi = hip.GemmEpilogue(logsoftmax=True)
+        lp = hip.gemm(a, w, transB=True, bias=b, tile=5, epilogue=epi)
+        torch.cuda.synchronize()
+        assert epi.served == hip.EPI_LOGSOFTMAX
+        ref = torch.log_softmax(a.double() @ w.double().t() + b.double(), dim=1)
+        assert (lp.double() - ref).abs().max().item() < 5e-5
+
+
+def test_mlp_out_bwd_exception_leaves_nothing_armed(hip, epi_ops, monkeypatch):
+    """The da2 GEMM of model._mlp_out_bwd_unfused raising with its column-sum request attached
+    leaves nothing behind: the next pair-path GEMM writes its own output alone -- a canary of
+    the size the column sums would have had stays intact -- and gives the plain product."""
+    import model
+    a, w, plain = epi_ops
+    bf = torch.bfloat16
+    M = D = Q = 256
+    dz = _rand(M, Q, seed=34).to(DEV, bf)
+    a1 = _rand(M, D, seed=35).to(DEV, bf)
+    a2 = _rand(M, D, seed=36).to(DEV, bf)
+    wo_t = _rand(D, Q, seed=37).to(DEV, bf)
+    real = hip.gemm
+
+    def gemm(*args, **kw):
+        if kw.get('epilogue') is not None:
+            raise RuntimeError('boom')
+        return real(*args, **kw)
+    monkeypatch.setattr(model.H, 'gemm', gemm)
+    with pytest.raises(RuntimeError, match='boom'):
+        model._mlp_out_bwd_unfused(bf, M, D, Q, dz, a1, a2, None, (None, wo_t), None, True)
+    monkeypatch.setattr(model.H, 'gemm', real)
+    canary = torch.full((M // 128, D), float('nan'), device=DEV)
+    before = _epi_bits(canary).clone()
+    c = hip.gemm(a[:256], w, transB=True, out_dtype=bf, tile=5)
+    torch.cuda.synchronize()
+    assert torch.equal(_epi_bits(canary), before)
+    assert torch.equal(c, plain[256])

@@ -56,18 +56,17 @@ def main(reps=10):
             try:
                 ts = []
                 for r in range(reps + 1):
+                    epi = None
                     if want_amax:
                         amax.zero_()
-                        H.lib().call('srnn_gemm_amax_next', H.ptr(amax))
+                        epi = H.GemmEpilogue(amax=amax)
                     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     e0.record(s)
                     if mbits is not None:
-                        H.gemm(da2, Wt, transB=True, mask_bits=mbits, out_dtype=bf)
+                        H.gemm(da2, Wt, transB=True, mask_bits=mbits, out_dtype=bf, epilogue=epi)
                     else:
-                        H.gemm(da2, Wt, transB=True, mask=mask, out_dtype=bf)
+                        H.gemm(da2, Wt, transB=True, mask=mask, out_dtype=bf, epilogue=epi)
                     e1.record(s)
-                    if want_amax:
-                        H.lib().dll.srnn_gemm_amax_taken()
                     e1.synchronize()
                     if r:
                         ts.append(e0.elapsed_time(e1))

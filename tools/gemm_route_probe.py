@@ -1,5 +1,5 @@
 """Per-call GEMM routing probe of the TBPTT step: records every plain H.gemm call of one eager
-bench step (no mask / bit mask / pending epilogue request -- those must stay on gemm3) at
+bench step (no mask / bit mask / epilogue request -- those must stay on gemm3) at
 --rows B, then times each call five ways, interleaved, HIP events, min of three rounds:
   default   the library's own route (hipBLASLt for large plain bf16 problems, else gemm3 /
             gemm2 / skinny),
@@ -52,28 +52,14 @@ def main():
     batches = bench.gpu_batches(bench.synth_batches(a.rows, bench.T_SEQ, 64, 2, 0), dev)
     calls = []
     orig = H.gemm
-    # an epilogue request (max |C|, column sums, log-softmax) binds the next GEMM to gemm3:
-    # such calls are not routing candidates
-    pend = [False]
     lib = H.lib()
-    ocall = lib.call
-
-    def call(name, *args):
-        if name in ('srnn_gemm_amax_next', 'srnn_gemm_amax_blk_next', 'srnn_gemm_csum_next'):
-            pend[0] = True
-        return ocall(name, *args)
-    lib.call = call
-    olsm = lib.dll.srnn_gemm_logsoftmax_next
-
-    def lsm_next():
-        pend[0] = True
-        return olsm()
-    lib.dll.srnn_gemm_logsoftmax_next = lsm_next
 
     def rec(x, y, **kw):
+        # an epilogue request (max |C|, column sums, log-softmax) binds its GEMM to gemm3: such
+        # calls are not routing candidates
         plain = (kw.get('mask') is None and kw.get('mask_bits') is None and
-                 kw.get('bits_out') is None and kw.get('batch', 1) == 1 and not pend[0])
-        pend[0] = False
+                 kw.get('bits_out') is None and kw.get('batch', 1) == 1 and
+                 kw.get('epilogue') is None)
         out = orig(x, y, **kw)
         if plain and len(calls) < 400:
             # the call's own tensors (views included: lda / ldb / ldc refer to their storage;
@@ -86,8 +72,6 @@ def main():
     tr.train()
     torch.cuda.synchronize()
     H.gemm = orig
-    lib.call = ocall
-    lib.dll.srnn_gemm_logsoftmax_next = olsm
     print('rows %d: %d plain gemm calls recorded' % (a.rows, len(calls)), flush=True)
     res = {}
     for rnd in range(3):

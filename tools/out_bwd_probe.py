@@ -26,10 +26,8 @@ def operands(M, D):
 
 
 def da2_call(dz, a2, wt, csp):
-    H.lib().call('srnn_gemm_csum_next', H.ptr(csp))
-    out = H.gemm(dz, wt, transB=True, mask=a2, out_dtype=torch.bfloat16)
-    H.lib().dll.srnn_gemm_csum_taken()
-    return out
+    return H.gemm(dz, wt, transB=True, mask=a2, out_dtype=torch.bfloat16,
+                  epilogue=H.GemmEpilogue(csum=csp))
 
 
 def timed(fn, reps=10):
