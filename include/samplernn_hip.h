@@ -538,6 +538,59 @@ int srnn_sample_rows(const float* logits, int64_t ld, int rows, const float* noi
                      int row0, int step, const float* temperature, const int32_t* top_k,
                      const float* top_p, int64_t* index, float* logp, void* stream);
 
+/* ---- streaming: carried state and a forced prefix ------------------------------------------
+ * Bytes of the opaque recurrent state of n_seqs rows of model m as srnn_generate5 reads and
+ * writes it: row-major, one record per row, so the result is a multiple of n_seqs and the row
+ * stride is the quotient.  A record depends on its row's history only: callers may reorder,
+ * drop or duplicate rows by moving whole records.  0: bad arguments.  A record holds a header
+ * (layout tag, dtype, n_tiers, n_rnn, dim, lookback L, fold flags, the row's completed step
+ * count as int64), the row's last L sample indices, every tier / layer's fp32 hidden state and,
+ * where a tier's tick is folded, the h W_hh^T + b_hh rows its next tick
+ * takes.  The layout depends on the model, its dtype and the fold decisions (environment
+ * switches such as SRNN_GEN_FOLD among them).                                                */
+size_t srnn_gen_state_bytes(const SrnnModel* m, int n_seqs);
+
+typedef struct SrnnGenStream {
+    const void* state_in;      /* device: state to continue from, or NULL = fresh start (h0,
+                                * q_zero history as pre-filled by the caller)                  */
+    void* state_out;           /* device: receives the state the call ends in, or NULL; may
+                                * alias state_in                                              */
+    size_t state_bytes;        /* size of either buffer: srnn_gen_state_bytes(m, n_seqs)       */
+    uint32_t step0;            /* generation steps the stream completed before this call: the
+                                * Philox step of the call's sample t is step0 + t              */
+    const int32_t* n_forced;   /* device (n_seqs) forced prefix lengths, or NULL (= 0)         */
+} SrnnGenStream;
+
+/* srnn_generate4 that may continue a stream and may be forced along a given prefix.  With st
+ * NULL, or all of its fields 0 / NULL, it is exactly srnn_generate4 (same kernels).
+ *   state_in   the call starts from these records in place of h0 / the pre-filled history: seq
+ *              columns [0, L) are WRITTEN by the call from the records.  Every record's header
+ *              must match the call's model, dtype and fold decisions, else the call fails with
+ *              return code 1 and a message, before anything is written.
+ *   state_out  the records of the state after the call's n_cond * L steps; a row's step count is
+ *              its state_in count (0 on a fresh start) plus n_cond * L.
+ *   step0      only moves the Philox counters (step0 + n_cond * L must fit 32 bits, else return
+ *              code 1).  A replayed `noise` buffer and `logp` stay indexed from the call's own
+ *              first step.  At step0 = 0 the draws are srnn_generate4's.
+ *   n_forced   the caller pre-fills seq columns [L, L + n_forced[b]) of row b.  At those steps
+ *              the row's logits, log-probs (`logp`) and noise consumption are what they would be
+ *              anyway, but the step's sample is the given one in place of the draw (whatever
+ *              temperature, top_k and top_p say) and seq is not written; the history the tiers
+ *              and the following steps see is the forced one.  Values are clamped to
+ *              [0, n_cond * L]; callers check the domain, and that the given samples lie in
+ *              [0, Q) (Generator.__call__ does).  Given, it selects the samplers' controlled
+ *              instantiations (level 1, or 2 with top_p) with temperature 1 and top-k off for the
+ *              arrays that are NULL; n_cond * L must then be below 2^23.
+ * A stream generated as consecutive calls, each continuing from the previous call's state_out
+ * with its own slice of cond (and of a replayed noise buffer), equals the single call over all
+ * the frames bit for bit, indices and log-probs: the calls split the stream at top-tier period
+ * boundaries, where every tier ticks and nothing but the recorded state is carried.          */
+int srnn_generate5(const SrnnModel* m, int n_seqs, int n_cond, const float* cond,
+                   const float* row_bias, const float* noise, uint64_t seed, int row0,
+                   int64_t* seq, float* logp, void* workspace, size_t workspace_bytes, int flags,
+                   void* stream, const float* temperature, const int32_t* top_k,
+                   const float* top_p, const SrnnGenStream* st);
+
 #ifdef __cplusplus
 }
 #endif

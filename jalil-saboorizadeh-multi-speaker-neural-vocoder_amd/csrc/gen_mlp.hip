@@ -633,7 +633,11 @@ __global__ __launch_bounds__(gm::NTHR, 2) void gen_mlp_kernel(GenMlpArgs a) {
         if (tid < min(R, 8)) {
             const int b = min(g * R + tid, B - 1);
             ctl[2 * tid] = (int)__float_as_uint(a.temperature ? a.temperature[b] : 1.0f);
-            ctl[2 * tid + 1] = a.top_k ? a.top_k[b] : 0;
+            // (the k slot also carries the row's forced prefix length: k is "off" outside
+            //  [1, 255], so it fits 8 bits and the length takes the 24 above them)
+            const int kb = a.top_k ? a.top_k[b] : 0;
+            const int nf = a.n_forced ? min(max(a.n_forced[b], 0), (1 << 23) - 1) : 0;
+            ctl[2 * tid + 1] = (int)((uint32_t)(kb >= 1 && kb <= 255 ? kb : 0) | ((uint32_t)nf << 8));
             if constexpr (CT == 2)
                 ctl[16 + tid] = (int)__float_as_uint(a.top_p ? a.top_p[b] : 1.0f);
         }
@@ -896,10 +900,14 @@ __global__ __launch_bounds__(gm::NTHR, 2) void gen_mlp_kernel(GenMlpArgs a) {
             x1 = hx_get2(rxz, zoff + 1024);
             // the row's noise: precomputed by gen_noise_kernel (loaded under the z hand-off)
             // or drawn here, under the first poll
+            // (the plain builds' own draw has no step origin -- they stay the code they were,
+            //  instruction for instruction: a streamed call at CT = 0 always comes with a.lq,
+            //  whose producers add it; gen_mlp_launch checks)
             floatx4 lq = floatx4{0.f, 0.f, 0.f, 0.f};
             if (valid)
                 lq = a.lq ? *reinterpret_cast<const floatx4*>(a.lq + ((int64_t)s * B + b) * Q + 4 * lane)
-                          : log_noise(sample_noise(a.noise, a.seed, B, b, i - a.L, lane, a.row0));
+                          : log_noise(sample_noise(a.noise, a.seed, B, b, i - a.L, lane, a.row0,
+                                                       CT != 0 ? a.step0 : 0u));
             if (!zcheck()) {
                 int spins = 0;
                 for (;;) {
@@ -913,22 +921,28 @@ __global__ __launch_bounds__(gm::NTHR, 2) void gen_mlp_kernel(GenMlpArgs a) {
             float* lrow = (p == 0 && valid && a.logp)
                               ? a.logp + ((int64_t)(i - a.L) * B + b) * Q : nullptr;
             int x;
+            bool forced = false;
             if constexpr (CT != 0) {
                 // the row's controls, from LDS (tau scales log q at the point of use, so lq
                 // keeps its meaning whether drawn ahead or here)
                 const int rc = __builtin_amdgcn_readfirstlane(min(r, 7));
                 const int2 ck = *reinterpret_cast<const int2*>(ctl + 2 * rc);
+                const int kk = ck.y & 255;
                 if constexpr (CT == 2)
-                    x = sample_row_ctrl(v, lq, __uint_as_float((uint32_t)ck.x), ck.y,
+                    x = sample_row_ctrl(v, lq, __uint_as_float((uint32_t)ck.x), kk,
                                         __uint_as_float((uint32_t)ctl[16 + rc]), lrow, lane);
                 else
-                    x = sample_row_ctrl(v, lq, __uint_as_float((uint32_t)ck.x), ck.y, lrow, lane);
+                    x = sample_row_ctrl(v, lq, __uint_as_float((uint32_t)ck.x), kk, lrow, lane);
+                // forced prefix: the step keeps the caller's sample (the log-probs above are
+                // written, the noise was consumed); wave-uniform, before hist is written
+                forced = i - a.L < (int)((uint32_t)ck.y >> 8);
+                if (forced) x = (int)a.seq[(int64_t)min(b, B - 1) * a.ldseq + i] & (Q - 1);
             } else {
                 x = sample_row(v, lq, lrow, lane);
             }
             if (lane == 0) {
                 hist[r * gm::HIST + (i & (gm::HIST - 1))] = x;
-                if (p == 0 && valid) a.seq[(int64_t)b * a.ldseq + i] = x;
+                if (p == 0 && valid && !forced) a.seq[(int64_t)b * a.ldseq + i] = x;
             }
             if (r == wave) xw = x;
         }
@@ -994,20 +1008,20 @@ __global__ __launch_bounds__(256) void gen_noise_kernel(const float* __restrict_
                                                         uint64_t seed, int row0,
                                                         const int* __restrict__ base,
                                                         int off, int nsteps, int L, int B,
-                                                        float* __restrict__ lq) {
+                                                        float* __restrict__ lq, uint32_t step0) {
     const int idx = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (idx >= nsteps * B) return;
     const int s = idx / B, b = idx - s * B;
     const int i = *base + off + s;
     *reinterpret_cast<floatx4*>(lq + ((int64_t)s * B + b) * gm::Q + 4 * lane) =
-        log_noise(sample_noise(noise, seed, B, b, i - L, lane, row0));
+        log_noise(sample_noise(noise, seed, B, b, i - L, lane, row0, step0));
 }
 
 int gen_noise_launch(const float* noise, uint64_t seed, int row0, const int* base, int off,
-                     int nsteps, int L, int B, float* lq, hipStream_t s) {
+                     int nsteps, int L, int B, float* lq, uint32_t step0, hipStream_t s) {
     if (nsteps <= 0 || B <= 0) return 0;
     hipLaunchKernelGGL(gen_noise_kernel, dim3(cdiv((int64_t)nsteps * B, 4)), dim3(256), 0, s,
-                       noise, seed, row0, base, off, nsteps, L, B, lq);
+                       noise, seed, row0, base, off, nsteps, L, B, lq, step0);
     SRNN_LAUNCH_CHECK();
     return 0;
 }
@@ -1233,7 +1247,7 @@ int gen_mlp_launch(const GenMlpPlan* pl, GenMlpArgs a, hipStream_t s) {
     // SRNN_GEN_LOCAL=0 only forces the global-mode hand-offs
     SRNN_REQUIRE(a.census && pl->G * pl->P <= HX_KEYED_WORDS, "gen_mlp: no census array");
     a.nolocal = pl->local ? 0 : 1;
-    SRNN_REQUIRE(pl->ctrl == (a.top_p ? 2 : (a.temperature || a.top_k) ? 1 : 0),
+    SRNN_REQUIRE(pl->ctrl == (a.top_p ? 2 : (a.temperature || a.top_k || a.n_forced) ? 1 : 0),
                  "gen_mlp: plan and sampling-control arrays disagree");
     {
         // SRNN_GEN_DIAG=1: phase timestamps of the first launch into a device buffer that
@@ -1250,6 +1264,8 @@ int gen_mlp_launch(const GenMlpPlan* pl, GenMlpArgs a, hipStream_t s) {
             gm_diag_buf() = diag;
         }
     }
+    SRNN_REQUIRE(pl->ctrl != 0 || a.step0 == 0 || a.lq,
+                 "gen_mlp: the plain loop's own draw has no step origin (noise must be drawn ahead)");
     const bool tg = a.tg.N > 0;
     if (tg) {
         SRNN_REQUIRE(pl->kernel_tg && a.wfr_hid && a.wfr_out,

@@ -25,7 +25,7 @@ int srnn_sample_impl(const float* z, int64_t ldz, int B, const float* noise, uin
                      int row0,
                      const int* base, int off, int L, int64_t* seq, int64_t ldseq,
                      float* logp_out, const float* temperature, const int* top_k,
-                     const float* top_p, hipStream_t s);
+                     const float* top_p, uint32_t step0, const int* n_forced, hipStream_t s);
 int srnn_gru_cell_impl(int dtype, int B, int D, int Din, const void* x, int64_t ldx,
                        const void* wih, const float* bih, const float* gi, int64_t ldgi,
                        const void* h, int64_t ldh, const float* hf, int64_t ldhf, const void* whh,
@@ -85,6 +85,7 @@ struct NoiseJob {
     int row0;                // global index of row 0 (Philox counters)
     int nsteps;              // 0: no noise work
     float* lq;               // (nsteps, B, Q)
+    uint32_t step0;          // Philox step of the call's first sample (streaming)
 };
 
 // noise plane z >= 1 of a 256-thread launch: one wave per (step, row)
@@ -97,7 +98,7 @@ __device__ __forceinline__ void noise_plane(const NoiseJob& nz, const int* base,
     const int st = idx / B, b = idx - st * B;
     const int i = *base + off + st;
     *reinterpret_cast<floatx4*>(nz.lq + ((int64_t)st * B + b) * 256 + 4 * lane) =
-        log_noise(sample_noise(nz.noise, nz.seed, B, b, i - L, lane, nz.row0));
+        log_noise(sample_noise(nz.noise, nz.seed, B, b, i - L, lane, nz.row0, nz.step0));
 }
 
 constexpr int TI_RB = 8, TI_OB = 64;
@@ -321,6 +322,93 @@ __global__ void copy_cast_kernel(const float* __restrict__ src, T* __restrict__ 
     if (e < n) dst[e] = from_f<T>(src[e]);
 }
 
+// ---- carried state (srnn_generate5) -----------------------------------------------------
+// One record per row, in 4-byte words:
+//   [0, 16)   header: tag, dtype, n_tiers, n_rnn, dim, L, fold flags, 0, steps (int64), 0...
+//   [16, +L)  the row's last L sample indices (int32)
+//   then      h of every (tier, layer), fp32, D each
+//   then      fold only: gh of the next bottom tick (3D), gh1 of the next upper tick (3D)
+// The T copies of h are not stored: every producer (fold_gru_kernel, the in-launch gate update,
+// the GRU cell kernels) writes from_f<T>(h) beside the fp32 h, and so does the unpack.  The gh
+// rows ARE stored: at a fresh start linear_fwd computes them, mid-stream the concatenated-weight
+// GEMMs do, and the two need not agree to the bit.
+constexpr uint32_t GS_TAG = 0x314E5253u;       // "SRN1"
+constexpr int GS_HDR = 16;
+struct GenStateMap {
+    int L, D, n_h, fold;
+    float* h[SRNN_MAX_TIERS * SRNN_MAX_RNN];    // pack: the live buffer; unpack: buffer [0]
+    void* hlp[SRNN_MAX_TIERS * SRNN_MAX_RNN];   // unpack: the T copy, or null (fp32: h itself)
+    float* gh0;
+    int64_t ldgh0;
+    float* gh1;
+    int64_t ldgh1;
+    uint32_t hdr[8];                            // words [0, 8) of a record of this call
+};
+
+// grid (words of a record / 256, B): word w of row b
+template <typename T>
+__global__ __launch_bounds__(256) void gen_state_unpack_kernel(
+    const uint32_t* __restrict__ st, int64_t rw, GenStateMap mp, int64_t* __restrict__ seq,
+    int64_t ldseq) {
+    int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x - GS_HDR;
+    const int b = blockIdx.y;
+    if (w < 0 || w + GS_HDR >= rw) return;
+    const uint32_t v = st[(int64_t)b * rw + GS_HDR + w];
+    if (w < mp.L) {
+        seq[(int64_t)b * ldseq + w] = (int64_t)(v & 255u);
+        return;
+    }
+    w -= mp.L;
+    const int D = mp.D;
+    if (w < (int64_t)mp.n_h * D) {
+        const int j = (int)(w / D), u = (int)(w - (int64_t)j * D);
+        const float f = __uint_as_float(v);
+        mp.h[j][(int64_t)b * D + u] = f;
+        if (mp.hlp[j]) ((T*)mp.hlp[j])[(int64_t)b * D + u] = from_f<T>(f);
+        return;
+    }
+    w -= (int64_t)mp.n_h * D;
+    if (!mp.fold) return;
+    if (w < 3 * D) mp.gh0[(int64_t)b * mp.ldgh0 + w] = __uint_as_float(v);
+    else if (w < 6 * D) mp.gh1[(int64_t)b * mp.ldgh1 + (w - 3 * D)] = __uint_as_float(v);
+}
+
+// The reverse; st_in (or null: a fresh start) supplies the rows' earlier step counts and may be
+// st_out itself: only the thread that writes a row's count reads it.
+__global__ __launch_bounds__(256) void gen_state_pack_kernel(
+    uint32_t* __restrict__ st_out, const uint32_t* st_in, int64_t rw, GenStateMap mp,
+    const int64_t* __restrict__ seq, int64_t ldseq, int64_t T) {
+    int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int b = blockIdx.y;
+    if (w >= rw) return;
+    uint32_t* o = st_out + (int64_t)b * rw;
+    if (w < GS_HDR) {
+        if (w == 8) {
+            int64_t steps = T;
+            if (st_in) steps += *reinterpret_cast<const int64_t*>(st_in + (int64_t)b * rw + 8);
+            *reinterpret_cast<int64_t*>(o + 8) = steps;
+        } else if (w != 9) {
+            o[w] = w < 8 ? mp.hdr[w] : 0u;
+        }
+        return;
+    }
+    w -= GS_HDR;
+    const int D = mp.D;
+    uint32_t v = 0u;
+    if (w < mp.L) {
+        v = (uint32_t)seq[(int64_t)b * ldseq + (ldseq - mp.L) + w];
+    } else if (w - mp.L < (int64_t)mp.n_h * D) {
+        const int64_t e = w - mp.L;
+        const int j = (int)(e / D), u = (int)(e - (int64_t)j * D);
+        v = __float_as_uint(mp.h[j][(int64_t)b * D + u]);
+    } else if (mp.fold) {
+        const int64_t e = w - mp.L - (int64_t)mp.n_h * D;
+        if (e < 3 * D) v = __float_as_uint(mp.gh0[(int64_t)b * mp.ldgh0 + e]);
+        else if (e < 6 * D) v = __float_as_uint(mp.gh1[(int64_t)b * mp.ldgh1 + (e - 3 * D)]);
+    }
+    o[GS_HDR + w] = v;
+}
+
 namespace {
 
 constexpr size_t ALIGN = 256;
@@ -467,6 +555,8 @@ struct Ctx {
     const float* temperature = nullptr;   // per-row sampling controls (device, n_seqs), or null
     const int* top_k = nullptr;
     const float* top_p = nullptr;         // nucleus mass (device, n_seqs), or null
+    uint32_t step0 = 0;                   // Philox step of sample L (steps done before the call)
+    const int* n_forced = nullptr;        // per-row forced prefix lengths (device), or null
     hipStream_t s;
     const GenMlpPlan* pl;     // persistent sample loop, or null for per-sample kernels
     // lq holds the draws of block-relative steps [noise_beg, noise_end): drawn ahead by the
@@ -495,7 +585,7 @@ int tier_tick(Ctx& c, int k, int off, int par) {
         // then [up | gh'] = h [W_up; W_hh]^T + [b_up; b_hh]
         const SrnnTier& u = m->tier[1];
         const int fi = (off / t.n_frame_samples) % u.frame_size;
-        const NoiseJob nz{c.noise, c.seed, c.row0, 0, nullptr};    // (the upper tick drew them)
+        const NoiseJob nz{c.noise, c.seed, c.row0, 0, nullptr, c.step0};    // (the upper tick drew them)
         const dim3 g2(cdiv(D, 256), cdiv(B, FG_RB));
         const int planes = 1;
         const int64_t fs0d = (int64_t)t.frame_size * D;
@@ -539,7 +629,7 @@ int tier_tick(Ctx& c, int k, int off, int par) {
     if (k == 1 && c.b.fold_top) {
         // folded top tick: a (+ the period's noise) -> gi = a Min1^T + P1, gh1 carried ->
         // [G | gh1'] = h [Wfold; W_hh1]^T + [bfold; b_hh1]
-        NoiseJob nz{c.noise, c.seed, c.row0, 0, nullptr};
+        NoiseJob nz{c.noise, c.seed, c.row0, 0, nullptr, c.step0};
         const int gx = cdiv(B, 2);
         int planes = 1;
         if (c.pl && c.b.lq && env_flag("SRNN_GEN_NOISE_AHEAD", 1)) {
@@ -586,7 +676,7 @@ int tier_tick(Ctx& c, int k, int off, int par) {
                 RET(srnn_raise_lds(dt == SRNN_F32 ? (const void*)tier_input_tiled_kernel<float>
                                                   : (const void*)tier_input_tiled_kernel<bf16>,
                                    160 * 1024));
-            NoiseJob nz{c.noise, c.seed, c.row0, 0, nullptr};
+            NoiseJob nz{c.noise, c.seed, c.row0, 0, nullptr, c.step0};
             int planes = 1;
             if (k == (c.b.fold ? 1 : 0) && c.pl && c.b.lq && env_flag("SRNN_GEN_NOISE_AHEAD", 1)) {
                 nz.nsteps = c.b.lq_steps;             // the persistent launches after this tick
@@ -657,7 +747,7 @@ int mlp_step(Ctx& c, int off) {
     RET(linear_fwd(dt, SRNN_F32, B, Q, D, c.b.a2, D, m->w_out, D, m->b_out, c.b.logits, Q, 0,
                    c.s));
     RET(srnn_sample_impl(c.b.logits, Q, B, c.noise, c.seed, c.row0, c.b.base, off, c.L, c.seq, c.ldseq,
-                         c.logp, c.temperature, c.top_k, c.top_p, c.s));
+                         c.logp, c.temperature, c.top_k, c.top_p, c.step0, c.n_forced, c.s));
     return 0;
 }
 
@@ -691,11 +781,14 @@ int run_block(Ctx& c, int periods) {
             a.xa1 = c.b.xa1; a.xa2 = c.b.xa2; a.xz = c.b.xz; a.err = c.b.gerr;
             a.census = c.b.gerr + 64;
             a.temperature = c.temperature; a.top_k = c.top_k; a.top_p = c.top_p;
-            if (c.b.lq && env_flag("SRNN_GEN_NOISE_AHEAD", 1)) {
+            a.step0 = c.step0; a.n_forced = c.n_forced;
+            // (a streamed call on the plain kernels always draws ahead: their in-loop draw,
+            //  kept as it was, knows no step origin)
+            if (c.b.lq && (env_flag("SRNN_GEN_NOISE_AHEAD", 1) || (c.step0 != 0 && !c.pl->ctrl))) {
                 // drawn ahead by a tick's input launch, else by a launch here
                 if (off < c.noise_beg || off + a.nsteps > c.noise_end) {
                     RET(gen_noise_launch(c.noise, c.seed, c.row0, c.b.base, off, a.nsteps, c.L, c.B,
-                                         c.b.lq, c.s));
+                                         c.b.lq, c.step0, c.s));
                     c.noise_beg = off;
                     c.noise_end = off + a.nsteps;
                 }
@@ -771,6 +864,27 @@ extern "C" int srnn_generate4(const SrnnModel* m, int n_seqs, int n_cond, const 
                               size_t workspace_bytes, int flags, void* stream,
                               const float* temperature, const int32_t* top_k,
                               const float* top_p);
+extern "C" int srnn_generate5(const SrnnModel* m, int n_seqs, int n_cond, const float* cond,
+                              const float* row_bias, const float* noise, uint64_t seed,
+                              int row0, int64_t* seq, float* logp, void* workspace,
+                              size_t workspace_bytes, int flags, void* stream,
+                              const float* temperature, const int32_t* top_k,
+                              const float* top_p, const SrnnGenStream* st);
+
+// words of a state record (even: the int64 step count stays 8-byte aligned in every row)
+static int64_t gen_state_row_words(const SrnnModel* m) {
+    const int64_t L = m->tier[m->n_tiers - 1].n_frame_samples;
+    const int64_t w = GS_HDR + L + (int64_t)m->n_tiers * m->n_rnn * m->dim +
+                      (fold_ok(m) ? 6 * (int64_t)m->dim : 0);
+    return (w + 1) & ~(int64_t)1;
+}
+
+extern "C" size_t srnn_gen_state_bytes(const SrnnModel* m, int n_seqs) {
+    if (!m || n_seqs <= 0 || m->n_tiers < 1 || m->n_tiers > SRNN_MAX_TIERS || m->n_rnn < 1 ||
+        m->n_rnn > SRNN_MAX_RNN || m->dim <= 0)
+        return 0;
+    return (size_t)gen_state_row_words(m) * 4 * (size_t)n_seqs;
+}
 
 extern "C" int srnn_generate(const SrnnModel* m, int n_seqs, int n_cond, const float* cond,
                              const float* row_bias, const float* noise, uint64_t seed,
@@ -809,6 +923,24 @@ extern "C" int srnn_generate4(const SrnnModel* m, int n_seqs, int n_cond, const 
                               size_t workspace_bytes, int flags, void* stream,
                               const float* temperature, const int32_t* top_k,
                               const float* top_p) {
+    return srnn_generate5(m, n_seqs, n_cond, cond, row_bias, noise, seed, row0, seq, logp,
+                          workspace, workspace_bytes, flags, stream, temperature, top_k, top_p,
+                          nullptr);
+}
+
+// srnn_generate4 that may start from a carried state (st->state_in), return the one it ends in
+// (st->state_out), draw its Philox noise from step st->step0 on, and keep the rows' first
+// st->n_forced[b] samples as given.  st null or all-default: srnn_generate4's launches.
+extern "C" int srnn_generate5(const SrnnModel* m, int n_seqs, int n_cond, const float* cond,
+                              const float* row_bias, const float* noise, uint64_t seed,
+                              int row0, int64_t* seq, float* logp, void* workspace,
+                              size_t workspace_bytes, int flags, void* stream,
+                              const float* temperature, const int32_t* top_k,
+                              const float* top_p, const SrnnGenStream* st) {
+    const void* state_in = st ? st->state_in : nullptr;
+    void* state_out = st ? st->state_out : nullptr;
+    const uint32_t step0 = st ? st->step0 : 0u;
+    const int* n_forced = st ? st->n_forced : nullptr;
     SRNN_REQUIRE(row0 >= 0, "generate: negative row offset");
     SRNN_REQUIRE(m && n_seqs > 0 && n_cond > 0 && seq && workspace, "generate: bad args");
     SRNN_REQUIRE(m->n_tiers >= 1 && m->n_tiers <= SRNN_MAX_TIERS, "generate: n_tiers");
@@ -818,13 +950,47 @@ extern "C" int srnn_generate4(const SrnnModel* m, int n_seqs, int n_cond, const 
     Ctx c;
     c.m = m;
     GenMlpPlan pl;
-    plan_for(m, n_seqs, top_p ? 2 : (temperature || top_k) ? 1 : 0, &pl);
+    plan_for(m, n_seqs, top_p ? 2 : (temperature || top_k || n_forced) ? 1 : 0, &pl);
     if (flags & 2) pl.ok = 0;          // caller asked for the per-sample kernel path
     size_t need = carve(m, n_seqs, (char*)workspace, &c.b, &pl);
     SRNN_REQUIRE(workspace_bytes >= need, "generate: workspace %zu < %zu", workspace_bytes, need);
     c.B = n_seqs;
     c.n_cond = n_cond;
     c.L = m->tier[m->n_tiers - 1].n_frame_samples;
+    const int64_t T = (int64_t)n_cond * c.L;
+    SRNN_REQUIRE((uint64_t)step0 + (uint64_t)T <= 0xFFFFFFFFull,
+                 "generate: step0 %u + %lld steps overflow the 32-bit Philox step counter", step0,
+                 (long long)T);
+    SRNN_REQUIRE(!n_forced || T < (1 << 23), "generate: a forced prefix needs fewer than 2^23 "
+                 "steps per call (%lld)", (long long)T);
+    const int64_t rw = gen_state_row_words(m);
+    SRNN_REQUIRE((!state_in && !state_out) ||
+                     st->state_bytes == (size_t)rw * 4 * (size_t)n_seqs,
+                 "generate: state of %zu bytes, this model / batch / fold layout needs %zu",
+                 st ? st->state_bytes : (size_t)0, (size_t)rw * 4 * (size_t)n_seqs);
+    SRNN_REQUIRE((((uintptr_t)state_in | (uintptr_t)state_out) & 7) == 0,
+                 "generate: state buffers must be 8-byte aligned");
+    c.step0 = step0;
+    c.n_forced = n_forced;
+    GenStateMap mp;
+    memset(&mp, 0, sizeof(mp));
+    mp.L = c.L;
+    mp.D = m->dim;
+    mp.n_h = m->n_tiers * m->n_rnn;
+    mp.fold = c.b.fold ? 1 : 0;
+    if (c.b.fold) {
+        mp.gh0 = c.b.up[0] + (size_t)m->tier[0].frame_size * m->dim;
+        mp.ldgh0 = c.b.ldup0;
+        mp.gh1 = c.b.fg + (size_t)m->tier[1].frame_size * 3 * m->dim;
+        mp.ldgh1 = c.b.ldg1;
+    }
+    mp.hdr[0] = GS_TAG;
+    mp.hdr[1] = (uint32_t)m->dtype;
+    mp.hdr[2] = (uint32_t)m->n_tiers;
+    mp.hdr[3] = (uint32_t)m->n_rnn;
+    mp.hdr[4] = (uint32_t)m->dim;
+    mp.hdr[5] = (uint32_t)c.L;
+    mp.hdr[6] = (c.b.fold ? 1u : 0u) | (c.b.fold_top ? 2u : 0u);
     c.cond = cond;
     c.row_bias = row_bias;
     c.noise = noise;
@@ -853,6 +1019,32 @@ extern "C" int srnn_generate4(const SrnnModel* m, int n_seqs, int n_cond, const 
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     do {
+        if (state_in) {
+            // every record's header must be one of this call's layout: checked on the host
+            // before anything is launched
+            std::vector<uint32_t> hd((size_t)B * 8);
+            if (hipMemcpy2DAsync(hd.data(), 32, state_in, (size_t)rw * 4, 32, B,
+                                 hipMemcpyDeviceToHost, s) != hipSuccess ||
+                hipStreamSynchronize(s) != hipSuccess) {
+                srnn_set_error("generate: reading the state headers: %s",
+                               hipGetErrorString(hipGetLastError()));
+                rc = 2;
+                break;
+            }
+            for (int b = 0; b < B && !rc; ++b) {
+                const uint32_t* h = hd.data() + (size_t)b * 8;
+                if (memcmp(h, mp.hdr, 32) != 0) {
+                    srnn_set_error(
+                        "generate: state row %d has layout (tag %08x, dtype %u, tiers %u, rnn %u, "
+                        "dim %u, L %u, fold %u), this call needs (tag %08x, dtype %u, tiers %u, "
+                        "rnn %u, dim %u, L %u, fold %u)", b, h[0], h[1], h[2], h[3], h[4], h[5],
+                        h[6], mp.hdr[0], mp.hdr[1], mp.hdr[2], mp.hdr[3], mp.hdr[4], mp.hdr[5],
+                        mp.hdr[6]);
+                    rc = 1;
+                }
+            }
+            if (rc) break;
+        }
         // 2 * udequantize LUT (bit-exact reference table for mu-law q = 256)
         {
             float lut2[256];
@@ -992,6 +1184,28 @@ extern "C" int srnn_generate4(const SrnnModel* m, int n_seqs, int n_cond, const 
                             t0.b_hh[0], c.b.up[0] + upw, c.b.ldup0, 0, s);
         }
         if (rc) break;
+        if (state_in) {
+            // the carried state replaces the fresh start's: buffer [0] of every h (and its T
+            // copy), the folded ticks' gh rows and the sample history seq[:, 0:L)
+            const bool lp = m->dtype != SRNN_F32;
+            for (int k = 0; k < m->n_tiers; ++k)
+                for (int l = 0; l < m->n_rnn; ++l) {
+                    mp.h[k * m->n_rnn + l] = c.b.h[k][l][0];
+                    mp.hlp[k * m->n_rnn + l] = lp ? c.b.hlp[k][l][0] : nullptr;
+                }
+            const dim3 grid(cdiv(rw, 256), B);
+            if (lp)
+                hipLaunchKernelGGL((gen_state_unpack_kernel<bf16>), grid, dim3(256), 0, s,
+                                   (const uint32_t*)state_in, rw, mp, seq, c.ldseq);
+            else
+                hipLaunchKernelGGL((gen_state_unpack_kernel<float>), grid, dim3(256), 0, s,
+                                   (const uint32_t*)state_in, rw, mp, seq, c.ldseq);
+            if (hipGetLastError() != hipSuccess) {
+                srnn_set_error("generate: state unpack launch");
+                rc = 2;
+                break;
+            }
+        }
         const bool use_graph = (flags & 1) != 0;
         int done = 0;
         const int nblocks = n_cond / 2;
@@ -1029,6 +1243,26 @@ extern "C" int srnn_generate4(const SrnnModel* m, int n_seqs, int n_cond, const 
             }
         }
         if (n_cond % 2) rc = run_block(c, 1);
+        if (!rc && state_out) {
+            // tick parity restarts at 0 in every block and the two-period blocks tick every tier
+            // an even number of times, so only a trailing one-period block moves a tier's live h:
+            // to buffer [1] where the tier ticks an odd number of times per period (the top tier
+            // always does)
+            for (int k = 0; k < m->n_tiers; ++k) {
+                const int live = (n_cond % 2) ? (c.L / m->tier[k].n_frame_samples) & 1 : 0;
+                for (int l = 0; l < m->n_rnn; ++l) {
+                    mp.h[k * m->n_rnn + l] = c.b.h[k][l][live];
+                    mp.hlp[k * m->n_rnn + l] = nullptr;
+                }
+            }
+            hipLaunchKernelGGL(gen_state_pack_kernel, dim3(cdiv(rw, 256), B), dim3(256), 0, s,
+                               (uint32_t*)state_out, (const uint32_t*)state_in, rw, mp, seq,
+                               c.ldseq, T);
+            if (hipGetLastError() != hipSuccess) {
+                srnn_set_error("generate: state pack launch");
+                rc = 2;
+            }
+        }
     } while (0);
     // the private stream is drained before its resources go (generation is one long call)
     if (hipStreamSynchronize(s) != hipSuccess && !rc) {

@@ -637,27 +637,31 @@ __global__ __launch_bounds__(256) void sample_kernel(
     uint64_t seed, int row0, const int* __restrict__ base, int off, int L,
     int64_t* __restrict__ seq, int64_t ldseq, float* __restrict__ logp_out,
     const float* __restrict__ temperature, const int* __restrict__ top_k,
-    const float* __restrict__ top_p) {
+    const float* __restrict__ top_p, uint32_t step0, const int* __restrict__ n_forced) {
     const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (b >= B) return;
     const int i = *base + off;        // absolute sample index being generated
-    const int step = i - L;
+    const int step = i - L;           // relative to the call; the Philox step is step0 + step
     const floatx4 v = *reinterpret_cast<const floatx4*>(z + (int64_t)b * ldz + 4 * lane);
-    const floatx4 lq = log_noise(sample_noise(noise, seed, B, b, step, lane, row0));
+    const floatx4 lq = log_noise(sample_noise(noise, seed, B, b, step, lane, row0, step0));
     float* lrow = logp_out ? logp_out + ((int64_t)step * B + b) * 256 : nullptr;
     const int bi = sample_draw<CT>(v, lq, b, temperature, top_k, top_p, lrow, lane);
+    // forced prefix (controlled instantiations): seq[b, i] stays as the caller gave it
+    if constexpr (CT != 0) {
+        if (n_forced && step < n_forced[b]) return;
+    }
     if (lane == 0) seq[(int64_t)b * ldseq + i] = bi;
 }
 
 int srnn_sample_impl(const float* z, int64_t ldz, int B, const float* noise, uint64_t seed,
                      int row0, const int* base, int off, int L, int64_t* seq, int64_t ldseq,
                      float* logp_out, const float* temperature, const int* top_k,
-                     const float* top_p, hipStream_t s) {
-    auto k = top_p ? sample_kernel<2> : (temperature || top_k) ? sample_kernel<1>
-                                                                : sample_kernel<0>;
+                     const float* top_p, uint32_t step0, const int* n_forced, hipStream_t s) {
+    auto k = top_p ? sample_kernel<2> : (temperature || top_k || n_forced) ? sample_kernel<1>
+                                                                            : sample_kernel<0>;
     hipLaunchKernelGGL(k, dim3(cdiv(B, 4)), dim3(256), 0, s, z, ldz, B, noise, seed, row0, base,
-                       off, L, seq, ldseq, logp_out, temperature, top_k, top_p);
+                       off, L, seq, ldseq, logp_out, temperature, top_k, top_p, step0, n_forced);
     SRNN_LAUNCH_CHECK();
     return 0;
 }

@@ -16,6 +16,8 @@ The drop-in classes call these ops, so the registered ops ARE the product path:
   srnn::generate                Generator.__call__'s sample loop (model.py:445-520)
   srnn::generate_ctrl           the same loop with per-row temperature / top-k in the draw
   srnn::generate_ctrl_p         ... and a per-row nucleus (top-p) cut-off
+  srnn::generate_stream         the loop over a chunk of a stream: carried state in / out, a
+                                Philox step origin, a forced prefix; optional controls
   srnn::sample_rows             the loops' row sampler on caller-chosen logits
 
 Every op has a fake (meta) kernel, so FakeTensor / torch.compile tracing sees shapes without
@@ -500,6 +502,110 @@ def _(weights, meta, cond, row_bias, noise, seed, row_offset, flags, return_logp
     return _generate_fake(meta, cond, return_logp)
 
 
+def gen_state_row_bytes(meta):
+    """Bytes of one row's record of the carried generation state (srnn_gen_state_bytes) for
+    model.generation_weights' meta, under the process's fold switches.  Reads the layout
+    integers only, so it also serves the fake registration."""
+    import ctypes
+    m = H.SrnnModel()
+    m.n_tiers, m.n_rnn, m.dim, m.q_levels, m.cond_dim, m.dtype = [int(v) for v in meta[:6]]
+    for k in range(m.n_tiers):
+        t = m.tier[k]
+        t.frame_size, t.n_frame_samples, t.in_dim, _ = [int(v) for v in meta[6 + 4 * k: 10 + 4 * k]]
+        t.b_up = 1               # (generation_weights always supplies the upsampling bias)
+    n = int(H.lib().dll.srnn_gen_state_bytes(ctypes.byref(m), 1))
+    if n <= 0:
+        raise ValueError('generate_stream: no state layout for this model')
+    return n
+
+
+@torch.library.custom_op('srnn::generate_stream', mutates_args=())
+def generate_stream(weights: list[Tensor], meta: list[int], cond: Tensor, row_bias: Tensor,
+                    noise: Optional[Tensor], seed: int, row_offset: int, flags: int,
+                    return_logp: bool, temperature: Optional[Tensor], top_k: Optional[Tensor],
+                    top_p: Optional[Tensor], state: Optional[Tensor], step0: int,
+                    prefix: Optional[Tensor], prefix_len: Optional[Tensor],
+                    return_state: bool) -> tuple[Tensor, Tensor, Tensor]:
+    """srnn::generate_ctrl_p over a chunk of a stream (srnn_generate5): every control is
+    optional (None = its default; all None: the plain kernels of srnn::generate), and
+      state       (n_seqs, row_bytes) uint8 records of an earlier call's end state to continue
+                  from, or None for a fresh start (h0, q_zero history)
+      step0       generation steps the stream completed before this call: the origin of the
+                  Philox counters (a replayed `noise` stays indexed from the call's first step)
+      prefix      (n_seqs, P) int64 sample indices, P <= T, or None; values are clamped to
+                  [0, Q)
+      prefix_len  (n_seqs,) int32 in [0, P]: row b's first prefix_len[b] steps take
+                  prefix[b] in place of the draw (log-probs and noise consumption unchanged);
+                  None = P for every row
+      return_state  also return the state the call ends in, else an empty tensor
+    Returns (seq (n_seqs, L + T) int64, logp (T, n_seqs, Q) or empty, state)."""
+    import ctypes
+    import model
+    n_seqs, num_cond = cond.shape[0], cond.shape[1]
+    dev = cond.device
+    ctl = [(n, t, dt) for n, t, dt in (('temperature', temperature, torch.float32),
+                                       ('top_k', top_k, torch.int32),
+                                       ('top_p', top_p, torch.float32)) if t is not None]
+    if prefix_len is not None:
+        if prefix is None:
+            raise ValueError('generate_stream: prefix_len without a prefix')
+        ctl.append(('prefix_len', prefix_len, torch.int32))
+    _check_rows('generate_stream', n_seqs, dev, *ctl)
+    m = model.srnn_model_struct(weights, meta)
+    L = m.tier[m.n_tiers - 1].n_frame_samples
+    T = num_cond * L
+    Q = m.q_levels
+    if step0 < 0 or step0 + T > 0xFFFFFFFF:
+        raise ValueError('generate_stream: step0 %d + %d steps do not fit the 32-bit counter'
+                         % (step0, T))
+    seq = torch.full((n_seqs, L + T), Q // 2, dtype=torch.long, device=dev)   # q_zero
+    n_forced = None
+    if prefix is not None:
+        if (prefix.dim() != 2 or prefix.shape[0] != n_seqs or prefix.shape[1] > T or
+                prefix.dtype != torch.int64 or prefix.device != dev):
+            raise ValueError('generate_stream: prefix must be an (n_seqs, <= %d) int64 tensor '
+                             'on %s' % (T, dev))
+        P = prefix.shape[1]
+        seq[:, L:L + P] = prefix.clamp(0, Q - 1)
+        n_forced = (prefix_len.clamp(0, P) if prefix_len is not None else
+                    torch.full((n_seqs,), P, dtype=torch.int32, device=dev)).contiguous()
+    row_bytes = int(H.lib().dll.srnn_gen_state_bytes(ctypes.byref(m), 1))
+    st = H.SrnnGenStream()
+    st.step0 = int(step0)
+    st.n_forced = H.ptr(n_forced)
+    if state is not None:
+        if (state.dtype != torch.uint8 or state.dim() != 2 or state.shape[0] != n_seqs or
+                state.device != dev):
+            raise ValueError('generate_stream: state must be an (n_seqs, row_bytes) uint8 tensor '
+                             'on %s' % dev)
+        state = state.contiguous()
+        st.state_in = H.ptr(state)
+        st.state_bytes = state.numel()
+    out_state = torch.empty((n_seqs, row_bytes) if return_state else (0,), dtype=torch.uint8,
+                            device=dev)
+    if return_state:
+        st.state_out = H.ptr(out_state)
+        if state is None:
+            st.state_bytes = out_state.numel()
+    logp = torch.empty((T, n_seqs, Q), device=dev) if return_logp else torch.empty(0, device=dev)
+    sz = ctypes.c_size_t(0)
+    H.lib().call('srnn_gen_workspace_size', ctypes.byref(m), n_seqs, ctypes.byref(sz))
+    ws = torch.empty(sz.value, device=dev, dtype=torch.uint8)
+    H.lib().call('srnn_generate5', ctypes.byref(m), n_seqs, num_cond, H.ptr(cond),
+                 H.ptr(row_bias), H.ptr(noise), int(seed) & ((1 << 64) - 1), int(row_offset),
+                 H.ptr(seq), H.ptr(logp) if return_logp else None, H.ptr(ws), sz.value, int(flags),
+                 H.stream(), H.ptr(temperature), H.ptr(top_k), H.ptr(top_p), ctypes.byref(st))
+    return seq, logp, out_state
+
+
+@generate_stream.register_fake
+def _(weights, meta, cond, row_bias, noise, seed, row_offset, flags, return_logp, temperature,
+      top_k, top_p, state, step0, prefix, prefix_len, return_state):
+    seq, logp = _generate_fake(meta, cond, return_logp)
+    rows = (cond.shape[0], gen_state_row_bytes(meta)) if return_state else (0,)
+    return seq, logp, cond.new_empty(rows, dtype=torch.uint8)
+
+
 @torch.library.custom_op('srnn::sample_rows', mutates_args=())
 def sample_rows(logits: Tensor, noise: Optional[Tensor], seed: int, row0: int, step: int,
                 temperature: Optional[Tensor], top_k: Optional[Tensor],
@@ -544,4 +650,4 @@ def _(logits, noise, seed, row0, step, temperature, top_k, top_p, return_logp):
 
 OPS = ('tier_fwd', 'tier_bwd', 'mlp_fwd', 'mlp_bwd', 'nll_bits', 'nll_bits_bwd', 'upsample',
        'upsample_bwd', 'dequant', 'adam_clip_', 'step_advance_', 'generate', 'generate_ctrl',
-       'generate_ctrl_p', 'sample_rows')
+       'generate_ctrl_p', 'generate_stream', 'sample_rows')

@@ -22,6 +22,10 @@ argmax(z - T log q) over the K largest logits; --temperature 0 is greedy (no ran
 --top_p P (default 1.0 = off, 0 < P <= 1) cuts the draw further to the nucleus: the most
 probable classes whose tempered mass reaches P.
 At the defaults the run is the reference's draw, bit for bit as before.
+--chunk_frames N (default 0 = the whole utterance in one call) generates N conditioning frames
+per call through Generator.stream, the recurrent state carried from call to call: the same
+WAV, byte for byte, with the sampler's host noise bounded by the chunk (single-process runs;
+rank-sharded batches are generated whole).
 """
 import argparse
 import os
@@ -69,7 +73,16 @@ default_params = {
     'temperature': 1.0,
     'top_k': 0,
     'top_p': 1.0,
+    'chunk_frames': 0,
 }
+
+
+def run_generator(gen, n_seqs, sample_length, cond, spk, chunk_frames, **kw):
+    """Generator.__call__, or the concatenated blocks of Generator.stream when chunk_frames is
+    set (equal bit for bit)."""
+    if chunk_frames > 0:
+        return torch.cat(list(gen.stream(n_seqs, cond, spk, chunk_frames, **kw)), dim=1)
+    return gen(n_seqs, sample_length, cond, spk, **kw)
 
 
 def init_random_seed(seed, cuda):
@@ -199,8 +212,9 @@ def main(frame_sizes, **params):
                                  sampler=params['sampler'], noise_rows=len(rows),
                                  seq_len=params['sample_length'], **ctrl).numpy()[:len(rows)]
         else:
-            out = gen(len(rows), params['sample_length'], rows, spks, sampler=params['sampler'],
-                      seed=params['seed'], **ctrl).numpy()
+            out = run_generator(gen, len(rows), params['sample_length'], rows, spks,
+                                params['chunk_frames'], sampler=params['sampler'],
+                                seed=params['seed'], **ctrl).numpy()
         if rank != 0:
             return
         L = model.lookback
@@ -218,10 +232,10 @@ def main(frame_sizes, **params):
         fname = output_name(params['model'], original, str(spk[speaker]))
         print('Generating file', fname)
         gen = Generator(model, use_cuda)
-        samples = gen(params['n_samples'], params['sample_length'], cond, speaker,
-                      sampler=params['sampler'], seed=params['seed'],
-                      temperature=params['temperature'], top_k=params['top_k'],
-                      top_p=params['top_p']).numpy()
+        samples = run_generator(gen, params['n_samples'], params['sample_length'], cond, speaker,
+                                params['chunk_frames'], sampler=params['sampler'],
+                                seed=params['seed'], temperature=params['temperature'],
+                                top_k=params['top_k'], top_p=params['top_p']).numpy()
         for i in range(params['n_samples']):
             write_wav(fname, samples[i, :], sr=params['sample_rate'])
 
@@ -250,7 +264,8 @@ def build_parser():
                       ('static_spk', parse_bool), ('seed', int), ('weight_norm', parse_bool),
                       ('cond_list', str), ('spk_list', str), ('sampler', str),
                       ('batch_files', parse_bool), ('compute_dtype', str),
-                      ('temperature', float), ('top_k', int), ('top_p', float)):
+                      ('temperature', float), ('top_k', int), ('top_p', float),
+                      ('chunk_frames', int)):
         p.add_argument('--' + name, type=typ)
     # gen.sh passes --results_path (generate.py has no such option; accepted and ignored)
     p.add_argument('--results_path', type=str)

@@ -1072,6 +1072,106 @@ def nucleus_control(n_seqs, top_p=1.0):
     return torch.from_numpy(p32.copy())
 
 
+def gen_state_layout(meta):
+    """[dtype, n_tiers, n_rnn, dim, lookback, row_bytes] of a GenState for generation_weights'
+    meta under the process's fold switches."""
+    import custom_ops
+    return [int(meta[5]), int(meta[0]), int(meta[1]), int(meta[2]), int(meta[-1]),
+            custom_ops.gen_state_row_bytes(meta)]
+
+
+class GenState:
+    """The recurrent state of n_seqs generation rows between two calls of Generator.__call__.
+
+    blob    (n_seqs, row_bytes) uint8: one opaque record per row as srnn_generate5 writes it
+            (header, last lookback samples, every tier's fp32 h, the folded ticks' carried
+            products; include/samplernn_hip.h).  A record depends on its row's history only.
+    layout  [dtype code, n_tiers, n_rnn, dim, lookback, row_bytes] the records were taken
+            under; the library checks each record's own header when it is used.
+    steps   (n_seqs,) int64 host tensor: generation steps each row has completed.
+    """
+
+    def __init__(self, blob, layout, steps):
+        layout = [int(v) for v in layout]
+        steps = torch.as_tensor(steps, dtype=torch.int64).reshape(-1).cpu()
+        if (not torch.is_tensor(blob) or blob.dtype != torch.uint8 or blob.dim() != 2 or
+                len(layout) != 6 or blob.shape[1] != layout[5] or
+                steps.shape[0] != blob.shape[0]):
+            raise ValueError('GenState: blob must be (n_seqs, row_bytes) uint8 with a 6-entry '
+                             'layout and one step count per row')
+        self.blob, self.layout, self.steps = blob, layout, steps
+
+    n_seqs = property(lambda self: self.blob.shape[0])
+    device = property(lambda self: self.blob.device)
+
+    def rows(self, index):
+        """The state of rows `index` (a sequence or tensor of row numbers, in that order:
+        a permutation, a subset, or repeats to fork one row into several continuations)."""
+        idx = torch.as_tensor(index, dtype=torch.long).reshape(-1).cpu()
+        if idx.numel() == 0 or int(idx.min()) < 0 or int(idx.max()) >= self.n_seqs:
+            raise IndexError('GenState.rows: row numbers must lie in [0, %d)' % self.n_seqs)
+        return GenState(self.blob[idx.to(self.blob.device)].contiguous(), self.layout,
+                        self.steps[idx].clone())
+
+    def to(self, device):
+        return GenState(self.blob.to(device), self.layout, self.steps)
+
+    def cpu(self):
+        return self.to('cpu')
+
+    def state_dict(self):
+        """Plain tensors and ints (torch.save-able); from_state_dict rebuilds the state."""
+        return {'blob': self.blob.detach().cpu().clone(), 'steps': self.steps.clone(),
+                'layout': list(self.layout)}
+
+    @classmethod
+    def from_state_dict(cls, d, device=None):
+        st = cls(d['blob'], d['layout'], d['steps'])
+        return st.to(device) if device is not None else st
+
+
+def forced_prefix(model, n_seqs, T, prefix, prefix_len):
+    """Generator.__call__'s prefix / prefix_len as host tensors ((n_seqs, P) int64,
+    (n_seqs,) int32 or None = all P), validated (a pure host function).  A floating-point
+    prefix is a waveform: quantised with the model's own quantiser."""
+    if prefix is None:
+        if prefix_len is not None:
+            raise ValueError('Generator: prefix_len given without a prefix')
+        return None, None
+    p = torch.as_tensor(np.asarray(prefix) if not torch.is_tensor(prefix) else prefix).cpu()
+    if p.dim() == 1:
+        p = p.unsqueeze(0).expand(n_seqs, -1)
+    if p.dim() != 2 or p.shape[0] != n_seqs or p.shape[1] > T:
+        raise ValueError('Generator: prefix has shape %s, expected (%d, <= %d)'
+                         % (tuple(p.shape), n_seqs, T))
+    Q = model.q_levels
+    if p.dtype.is_floating_point:
+        # (the quantiser maps a full-scale +1.0 to Q itself: held at the top level)
+        p = (utils.uquantize if model.ulaw else utils.linear_quantize)(p.contiguous(), Q)
+        p = p.clamp(0, Q - 1)
+    elif p.dtype == torch.bool or p.dtype.is_complex:
+        raise ValueError('Generator: prefix must hold sample indices or a float waveform')
+    p = p.to(torch.int64).contiguous()
+    P = p.shape[1]
+    if P and (int(p.min()) < 0 or int(p.max()) >= Q):
+        raise ValueError('Generator: prefix indices must lie in [0, %d)' % Q)
+    if prefix_len is None:
+        return p, None
+    a = (prefix_len.detach().cpu().numpy() if torch.is_tensor(prefix_len)
+         else np.asarray(prefix_len))
+    if a.dtype == object or a.dtype.kind not in 'iu':
+        raise ValueError('Generator: prefix_len must be integral')
+    if a.ndim == 0:
+        a = np.broadcast_to(a, (n_seqs,))
+    if a.ndim != 1 or a.shape[0] != n_seqs:
+        raise ValueError('Generator: prefix_len has shape %s, expected a scalar or (%d,)'
+                         % (tuple(a.shape), n_seqs))
+    a = a.astype(np.int64)
+    if np.any(a < 0) or np.any(a > P):
+        raise ValueError('Generator: prefix_len must lie in [0, %d]' % P)
+    return p, torch.from_numpy(a.astype(np.int32))
+
+
 class Generator(Runner):
     """model.py:439-520: autoregressive generation, the whole loop on the device.
 
@@ -1099,23 +1199,40 @@ class Generator(Runner):
     further, to the smallest set of most probable classes of the top-k set whose tempered mass
     exp((z - max z) / temperature), renormalised over that set, reaches top_p: the class that
     crosses top_p is included and ties at the cut are kept.  Greedy rows ignore it.
+
+    Streaming (not in the reference).  return_state=True appends a GenState to the result: the
+    rows' recurrent state after the call.  state=<GenState> starts the call from it in place of
+    h0 and the q_zero history, with `cond` holding the NEXT frames: an utterance generated as
+    consecutive calls over slices of cond (and of `noise`, when replayed) equals the single
+    call bit for bit, indices and log-probs.  Under sampler='philox' the device noise continues
+    from the state's step count, which must then be the same for every row (ValueError);
+    replayed noise has no such constraint.  prefix ((n_seqs, P) indices, or a float waveform
+    quantised with the model's quantiser; P <= T) with prefix_len (a scalar or one value per
+    row in [0, P]; default P) forces row b's first prefix_len[b] steps to the given samples:
+    log-probs are still reported and noise still consumed at those steps, and a forced step
+    overrides temperature, top_k and top_p.  stream() yields an utterance chunk by chunk,
+    prime() returns the state after given audio.
     """
 
     def __init__(self, model, cuda=False):
         super().__init__(model)
         self.cuda = cuda
         self.last_sequences = None
+        self.last_state = None
 
     def __call__(self, n_seqs, seq_len, cond, spk, sampler='torch', seed=0, noise=None,
                  return_logp=False, use_graph=True, dtype=None, persistent=True, row_offset=0,
-                 temperature=1.0, top_k=0, top_p=1.0):
+                 temperature=1.0, top_k=0, top_p=1.0, state=None, return_state=False,
+                 prefix=None, prefix_len=None):
         """row_offset: these n_seqs rows are rows [row_offset, row_offset + n_seqs) of a larger
         batch (rank-sharded generation, see shard_generate): the Philox noise (sampler='philox')
         is that of the global rows, so shards reproduce the single-process stream.
         temperature, top_k, top_p: the sampling controls (class docstring); at their defaults
         the call is the uncontrolled one, op and kernels, and with top_p at 1 it is the call
         without top_p.  return_logp's log-probs are the model's
-        log-softmax whatever the controls."""
+        log-softmax whatever the controls.
+        state, return_state, prefix, prefix_len: streaming (class docstring); at their defaults
+        the call launches exactly what it launches without them."""
         model = self.model
         self.reset_hidden_states()
         dev = next(model.parameters()).device
@@ -1145,11 +1262,26 @@ class Generator(Runner):
             assert noise.shape == (T, n_seqs, Q), 'noise must be (T, n_seqs, Q)'
         # the registered op srnn::generate (custom_ops.py): the whole sample loop on the device
         # (with sampling controls: srnn::generate_ctrl, the same loop with them in the draw)
+        streaming = (state is not None or return_state or prefix is not None or
+                     prefix_len is not None)
+        if streaming:
+            philox = noise is None
+            state_blob, step0 = self._stream_state(state, n_seqs, dev, philox)
+            prefix, prefix_len = forced_prefix(model, n_seqs, T, prefix, prefix_len)
         with torch.no_grad():
             args = (weights, meta, cond, row_bias, noise, int(seed) & ((1 << 63) - 1),
                     int(row_offset), (1 if use_graph else 0) | (0 if persistent else 2),
                     bool(return_logp))
-            if ctrl is None:
+            if streaming:
+                # srnn::generate_stream: the same loop from a carried state and / or along a
+                # forced prefix (srnn_generate5); controls at their defaults stay None
+                seq, logp, blob = torch.ops.srnn.generate_stream(
+                    *args, ctrl[0].to(dev) if ctrl is not None else None,
+                    ctrl[1].to(dev) if ctrl is not None else None,
+                    nucleus.to(dev) if nucleus is not None else None, state_blob, step0,
+                    prefix.to(dev) if prefix is not None else None,
+                    prefix_len.to(dev) if prefix_len is not None else None, bool(return_state))
+            elif ctrl is None:
                 seq, logp = torch.ops.srnn.generate(*args)
             elif nucleus is not None:
                 seq, logp = torch.ops.srnn.generate_ctrl_p(*args, ctrl[0].to(dev), ctrl[1].to(dev),
@@ -1159,9 +1291,78 @@ class Generator(Runner):
         assert utils.q_zero(Q) == Q // 2
         self.last_sequences = seq
         out = model.dequantize(seq[:, L:], Q).cpu()
+        res = (out,)
         if return_logp:
-            return out, logp.permute(1, 0, 2).contiguous()
-        return out
+            res += (logp.permute(1, 0, 2).contiguous(),)
+        if return_state:
+            before = state.steps if state is not None else torch.zeros(n_seqs, dtype=torch.int64)
+            res += (GenState(blob, gen_state_layout(meta), before + T),)
+        return res if len(res) > 1 else out
+
+    @staticmethod
+    def _stream_state(state, n_seqs, dev, philox):
+        """(records on the device or None, step0) of a call that continues `state`."""
+        if state is None:
+            return None, 0
+        if not isinstance(state, GenState):
+            raise TypeError('Generator: state must be a GenState')
+        if state.n_seqs != n_seqs:
+            raise ValueError('Generator: state holds %d rows, the call has %d'
+                             % (state.n_seqs, n_seqs))
+        step0 = 0
+        if philox:
+            # one step origin per call: the device noise of step t is Philox(row, step0 + t)
+            if bool((state.steps != state.steps[0]).any()):
+                raise ValueError('Generator: rows at differing step counts %s cannot continue '
+                                 'under sampler=\'philox\' (replayed noise can)'
+                                 % sorted(set(state.steps.tolist())))
+            step0 = int(state.steps[0])
+        return state.blob.to(dev), step0
+
+    def stream(self, n_seqs, cond, spk, chunk_frames, state=None, **kw):
+        """Generates chunk_frames conditioning frames per call of __call__, each continuing from
+        the state the previous one ended in, and yields every chunk's host float32
+        (n_seqs, frames * lookback) block as it completes (with return_logp: (block, logp)).
+        The concatenation equals the single __call__ over all of cond, for either sampler:
+        sampler='torch' draws each chunk's noise when the chunk starts -- the CPU generator's
+        exponential_ stream does not depend on how it is cut -- so host memory is bounded by
+        the chunk; a given `noise` is sliced.  The state after the last chunk is left in
+        self.last_state; `state` continues an earlier stream."""
+        chunk_frames = int(chunk_frames)
+        if chunk_frames < 1:
+            raise ValueError('Generator.stream: chunk_frames must be >= 1')
+        for name in ('return_state', 'prefix', 'prefix_len'):
+            if name in kw:
+                raise ValueError('Generator.stream: %s is not a stream argument' % name)
+        cond = torch.as_tensor(np.asarray(cond) if not torch.is_tensor(cond) else cond)
+        fdim = cond.dim() - 2                      # the frame axis of (F, C) or (n_seqs, F, C)
+        num_cond = cond.shape[fdim]
+        L = self.model.lookback
+        noise = kw.pop('noise', None)
+        logp = kw.get('return_logp', False)
+        for f0 in range(0, num_cond, chunk_frames):
+            f1 = min(num_cond, f0 + chunk_frames)
+            res = self(n_seqs, 0, cond.narrow(fdim, f0, f1 - f0), spk, state=state,
+                       return_state=True,
+                       noise=None if noise is None else noise[f0 * L:f1 * L], **kw)
+            state = res[-1]
+            self.last_state = state
+            yield (res[0], res[1]) if logp else res[0]
+
+    def prime(self, prefix, cond, spk, **kw):
+        """The GenState after the given audio: a call forced along all of `prefix` ((n_seqs, T)
+        indices or a float waveform, T = num_cond * lookback exactly), from which __call__ or
+        stream continues with further conditioning frames."""
+        prefix = torch.as_tensor(np.asarray(prefix) if not torch.is_tensor(prefix) else prefix)
+        if prefix.dim() == 1:
+            prefix = prefix.unsqueeze(0)
+        cond_t = torch.as_tensor(np.asarray(cond) if not torch.is_tensor(cond) else cond)
+        T = cond_t.shape[-2] * self.model.lookback
+        if prefix.dim() != 2 or prefix.shape[1] != T:
+            raise ValueError('Generator.prime: prefix of shape %s, expected (n_seqs, %d) = '
+                             'num_cond * lookback samples' % (tuple(prefix.shape), T))
+        kw.setdefault('sampler', 'philox')         # (every step is forced: no noise is needed)
+        return self(prefix.shape[0], 0, cond, spk, prefix=prefix, return_state=True, **kw)[-1]
 
 
 def shard_generate(generator, n_seqs, cond, spk, seed, rank=None, world=None, sampler='philox',

@@ -94,6 +94,9 @@ _SIGS = {
     'srnn_generate2': [_P, _I, _I, _P, _P, _P, _U64, _I, _P, _P, _P, _SZ, _I, _P],
     'srnn_generate3': [_P, _I, _I, _P, _P, _P, _U64, _I, _P, _P, _P, _SZ, _I, _P, _P, _P],
     'srnn_generate4': [_P, _I, _I, _P, _P, _P, _U64, _I, _P, _P, _P, _SZ, _I, _P, _P, _P, _P],
+    'srnn_generate5': [_P, _I, _I, _P, _P, _P, _U64, _I, _P, _P, _P, _SZ, _I, _P, _P, _P, _P,
+                       _P],
+    'srnn_gen_state_bytes': [_P, _I],          # (returns size_t, not a status: see _Lib)
     'srnn_sample_rows': [_P, _L, _I, _P, _U64, _I, _I, _P, _P, _P, _P, _P, _P],
     'srnn_persistent_flag_to_f32': [_P, _P],
     'srnn_persistent_flag_or_f32': [_P, _P],
@@ -123,6 +126,13 @@ class SrnnModel(ctypes.Structure):
     _fields_ = [('n_tiers', _I), ('n_rnn', _I), ('dim', _I), ('q_levels', _I),
                 ('cond_dim', _I), ('dtype', _I), ('tier', SrnnTier * MAX_TIERS),
                 ('tab', _P), ('w_hid', _P), ('b_hid', _P), ('w_out', _P), ('b_out', _P)]
+
+
+class SrnnGenStream(ctypes.Structure):
+    """The C ABI's SrnnGenStream (srnn_generate5): carried state in / out (device pointers or
+    None), their size, the Philox step origin and the rows' forced prefix lengths."""
+    _fields_ = [('state_in', _P), ('state_out', _P), ('state_bytes', _SZ),
+                ('step0', ctypes.c_uint32), ('n_forced', _P)]
 
 
 EPI_AMAX, EPI_BLK, EPI_CSUM, EPI_LOGSOFTMAX = 1, 2, 4, 8
@@ -170,6 +180,7 @@ class _Lib:
             fn = getattr(self.dll, name)
             fn.argtypes = args
             fn.restype = _I
+        self.dll.srnn_gen_state_bytes.restype = _SZ
         # query entry points called on .dll directly (pointers are passed as plain ints, so
         # every pointer argument needs its declared type)
         for name, args in (('srnn_gru_xcd_error', [_P]), ('srnn_persistent_error_take', []),
