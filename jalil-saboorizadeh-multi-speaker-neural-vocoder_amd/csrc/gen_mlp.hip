@@ -1069,17 +1069,6 @@ GmKernel pick(int upw, int nzt, int fs0, int D, int R) {
     if (fs0 == 16) return pick_t<T, 15, 16, CT>(upw, nzt);
     return fs0 - 1 <= 15 ? pick_t<T, 15, 0, CT>(upw, nzt) : pick_t<T, 31, 0, CT>(upw, nzt);
 }
-
-int device_cus() {
-    static int ncu = 0;
-    if (!ncu) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-            ncu = 0;
-    }
-    return ncu;
-}
 }  // namespace
 
 int gen_mlp_plan(int dtype, int B, int D, int FS0, int Q, int ctrl, GenMlpPlan* pl) {
@@ -1247,7 +1236,7 @@ int gen_mlp_launch(const GenMlpPlan* pl, GenMlpArgs a, hipStream_t s) {
     // SRNN_GEN_LOCAL=0 only forces the global-mode hand-offs
     SRNN_REQUIRE(a.census && pl->G * pl->P <= HX_KEYED_WORDS, "gen_mlp: no census array");
     a.nolocal = pl->local ? 0 : 1;
-    SRNN_REQUIRE(pl->ctrl == (a.top_p ? 2 : (a.temperature || a.top_k || a.n_forced) ? 1 : 0),
+    SRNN_REQUIRE(pl->ctrl == sample_ctrl_level(a.temperature, a.top_k, a.top_p, a.n_forced),
                  "gen_mlp: plan and sampling-control arrays disagree");
     {
         // SRNN_GEN_DIAG=1: phase timestamps of the first launch into a device buffer that
@@ -1279,15 +1268,7 @@ int gen_mlp_launch(const GenMlpPlan* pl, GenMlpArgs a, hipStream_t s) {
     const GmKernel k = (GmKernel)(tg ? pl->kernel_tg : pl->kernel);
     const size_t lds = tg ? pl->lds_tg : pl->lds;
     // raise the dynamic-LDS limit once per kernel (not inside a graph capture's launches)
-    static const void* done[64];
-    static size_t done_lds[64];
-    int slot = 0;
-    while (slot < 64 && done[slot] && done[slot] != (const void*)k) ++slot;
-    if (slot == 64 || !done[slot] || done_lds[slot] < lds) {
-        SRNN_CHECK_HIP(hipFuncSetAttribute((const void*)k,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        if (slot < 64) { done[slot] = (const void*)k; done_lds[slot] = 160 * 1024; }
-    }
+    if (const int rc = srnn_raise_lds((const void*)k, 160 * 1024)) return rc;
     if (srnn_persist_check((const void*)k, gm::NTHR, lds, (int64_t)pl->G * pl->P, "gen_mlp"))
         return 1;
     hipLaunchKernelGGL(k, dim3(pl->G * pl->P), dim3(gm::NTHR), lds, s, a);

@@ -452,20 +452,32 @@ struct Bufs {
     int64_t ldg1;            //  upper tick], ldg1 = FS1 3D + 3D
 };
 
+// The environment switches of the host driver, read once per call (tests flip them between
+// calls of one process) so that every layout decision of a call sees the same values.
+struct GenSwitches {
+    bool fold, fold_f32, fold_top, noise_ahead, fuse_gates, persist;
+    static GenSwitches read() {
+        return {env_flag("SRNN_GEN_FOLD", 1) != 0,        env_flag("SRNN_GEN_FOLD_F32", 1) != 0,
+                env_flag("SRNN_GEN_FOLD_TOP", 1) != 0,    env_flag("SRNN_GEN_NOISE_AHEAD", 1) != 0,
+                env_flag("SRNN_GEN_FUSE_GATES", 1) != 0,  env_flag("SRNN_GEN_PERSIST", 1) != 0};
+    }
+};
+
 // fp32 too (SRNN_GEN_FOLD_F32=0: unfolded fp32 ticks): the folds reassociate fp32 sums
 // (W_ih (W_in a + b) -> (W_ih W_in) a + W_ih b), same precision, rounding in the last bits
-bool fold_ok(const SrnnModel* m) {
+bool fold_ok(const SrnnModel* m, const GenSwitches& sw) {
     const SrnnTier& t = m->tier[0];
-    return (m->dtype == SRNN_BF16 || (env_flag("SRNN_GEN_FOLD_F32", 1) && m->dim % 64 == 0)) &&
+    return (m->dtype == SRNN_BF16 || (sw.fold_f32 && m->dim % 64 == 0)) &&
            m->n_tiers >= 2 &&
            m->n_rnn == 1 &&
            t.in_dim == t.n_frame_samples && t.n_frame_samples <= 16 && t.b_up &&
            m->tier[1].frame_size <= FOLD_MAX_FS1 &&
-           env_flag("SRNN_GEN_FOLD", 1);
+           sw.fold;
 }
 
 // carve (or size, if ws == nullptr) the workspace
-size_t carve(const SrnnModel* m, int B, char* ws, Bufs* b, const GenMlpPlan* pl) {
+size_t carve(const SrnnModel* m, int B, char* ws, Bufs* b, const GenMlpPlan* pl,
+             const GenSwitches& sw) {
     const int D = m->dim, Q = m->q_levels;
     const size_t es = m->dtype == SRNN_F32 ? 4 : 2;
     const bool lp = m->dtype != SRNN_F32;
@@ -485,7 +497,7 @@ size_t carve(const SrnnModel* m, int B, char* ws, Bufs* b, const GenMlpPlan* pl)
             }
         b->up[k] = (float*)take((size_t)B * (t.frame_size + 3) * D * 4);
     }
-    b->fold = fold_ok(m);
+    b->fold = fold_ok(m, sw);
     b->ldup0 = (int64_t)m->tier[0].frame_size * D + (b->fold ? 3 * D : 0);
     b->wcat = nullptr;
     b->wfold = nullptr;
@@ -506,8 +518,7 @@ size_t carve(const SrnnModel* m, int B, char* ws, Bufs* b, const GenMlpPlan* pl)
         b->bfold = (float*)take((size_t)b->ldg1 * 4);
         b->fg = (float*)take((size_t)B * b->ldg1 * 4);
         b->ticks = (GenMlpArgs::Tick*)take((size_t)2 * F1 * sizeof(GenMlpArgs::Tick));
-        b->fold_top = m->n_tiers == 2 && m->tier[1].in_dim <= TA_AP &&
-                      env_flag("SRNN_GEN_FOLD_TOP", 1);
+        b->fold_top = m->n_tiers == 2 && m->tier[1].in_dim <= TA_AP && sw.fold_top;
         if (b->fold_top) {
             b->min1 = take((size_t)3 * D * TA_AP * es);
             b->p1 = (float*)take((size_t)B * 3 * D * 4);
@@ -531,34 +542,92 @@ size_t carve(const SrnnModel* m, int B, char* ws, Bufs* b, const GenMlpPlan* pl)
         b->xa1 = (unsigned long long*)take(pl->xa_words * 8);
         b->xa2 = (unsigned long long*)take(pl->xa_words * 8);
         b->xz = (unsigned long long*)take(pl->xz_words * 8);
-        b->wfr_hid = pl->wfr_hid_bytes ? take(pl->wfr_hid_bytes) : nullptr;
-        b->wfr_out = pl->wfr_out_bytes ? take(pl->wfr_out_bytes) : nullptr;
         b->lq_steps = m->tier[0].frame_size * (b->fold ? m->tier[1].frame_size : 1);
         b->lq = (float*)take((size_t)b->lq_steps * B * Q * 4);
         b->gm_bytes = off - start;
+        // (after the block a call zeroes at its start: the images depend on the model alone)
+        b->wfr_hid = pl->wfr_hid_bytes ? take(pl->wfr_hid_bytes) : nullptr;
+        b->wfr_out = pl->wfr_out_bytes ? take(pl->wfr_out_bytes) : nullptr;
     }
     return off;
 }
 
-struct Ctx {
+// Everything one generation call is given (the arguments of srnn_generate5, st unpacked), in
+// the entries' parameter order: each extern "C" entry fills one by aggregate initialisation.
+struct GenRequest {
     const SrnnModel* m;
-    Bufs b;
-    int B, n_cond, L;
+    int n_seqs, n_cond;
     const float* cond;
     const float* row_bias;
     const float* noise;
     uint64_t seed;
-    int row0 = 0;             // global index of row 0 (rank-sharded generation)
+    int row0;                             // global index of row 0 (rank-sharded generation)
     int64_t* seq;
-    int64_t ldseq;
     float* logp;
+    void* workspace;
+    size_t workspace_bytes;
+    int flags;
+    hipStream_t stream;
     const float* temperature = nullptr;   // per-row sampling controls (device, n_seqs), or null
     const int* top_k = nullptr;
     const float* top_p = nullptr;         // nucleus mass (device, n_seqs), or null
+    const void* state_in = nullptr;       // carried state records (device), or null
+    void* state_out = nullptr;
+    size_t state_bytes = 0;
     uint32_t step0 = 0;                   // Philox step of sample L (steps done before the call)
     const int* n_forced = nullptr;        // per-row forced prefix lengths (device), or null
-    hipStream_t s;
-    const GenMlpPlan* pl;     // persistent sample loop, or null for per-sample kernels
+    int level() const { return sample_ctrl_level(temperature, top_k, top_p, n_forced); }
+};
+
+// f(T{}) launches a kernel's instantiation for T, the element type of `dtype`
+// (gemm_dispatch_types' idiom), and the launch is checked: a launch that differs between the
+// dtypes only in its casts is written once
+template <typename F>
+inline int gen_typed_launch(int dtype, F&& f) {
+    if (dtype == SRNN_F32) f(float{});
+    else f(bf16{});
+    SRNN_LAUNCH_CHECK();
+    return 0;
+}
+
+// The private stream a call runs on (so that a hipGraph can be captured whatever the caller's
+// stream is), the event that orders it after the caller's, and the captured block.  Released on
+// every path; gen_finish has drained the stream by then.
+struct GenStream {
+    hipStream_t s = nullptr;
+    hipEvent_t ev = nullptr;
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    GenStream() = default;
+    GenStream(const GenStream&) = delete;
+    GenStream& operator=(const GenStream&) = delete;
+    int open(hipStream_t user) {
+        SRNN_CHECK_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        SRNN_CHECK_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        SRNN_CHECK_HIP(hipEventRecord(ev, user));
+        SRNN_CHECK_HIP(hipStreamWaitEvent(s, ev, 0));
+        return 0;
+    }
+    ~GenStream() {
+        if (exec) (void)hipGraphExecDestroy(exec);
+        if (graph) (void)hipGraphDestroy(graph);
+        if (ev) (void)hipEventDestroy(ev);
+        if (s) (void)hipStreamDestroy(s);
+    }
+};
+
+struct Ctx {
+    const GenRequest& rq;
+    const GenSwitches sw;
+    GenStream gs;
+    Bufs b{};
+    int L = 0;                // the top tier's period
+    int64_t T = 0;            // steps of this call, n_cond L
+    int64_t ldseq = 0;
+    int64_t rw = 0;           // words of a state record
+    hipStream_t s = nullptr;  // the call's private stream
+    GenMlpPlan plan{};
+    const GenMlpPlan* pl = nullptr;   // &plan (persistent sample loop), or null: per-sample kernels
     // lq holds the draws of block-relative steps [noise_beg, noise_end): drawn ahead by the
     // input launch of the bottom tick (FS0 steps) or, with the folded bottom tick, of the
     // upper tier's tick (its whole period)
@@ -568,15 +637,19 @@ struct Ctx {
     // (GenMlpArgs::tg): set by tier_tick, consumed by that launch
     bool tick_gemm = false;
     GenMlpArgs::TickGemm pending{};
+    GenStateMap mp{};         // the call's state record layout (header, gh rows; h per use)
+    // a launch's noise source, drawing nothing ahead (the upper tick drew them) until given lq
+    NoiseJob noise_job() const { return {rq.noise, rq.seed, rq.row0, 0, nullptr, rq.step0}; }
 };
 
 #define RET(x) do { int _r = (x); if (_r) return _r; } while (0)
 
 // one tier tick at block-relative offset `off`; `par` = tick parity of this tier
 int tier_tick(Ctx& c, int k, int off, int par) {
-    const SrnnModel* m = c.m;
+    const GenRequest& r = c.rq;
+    const SrnnModel* m = r.m;
     const SrnnTier& t = m->tier[k];
-    const int D = m->dim, B = c.B, dt = m->dtype;
+    const int D = m->dim, B = r.n_seqs, dt = m->dtype;
     const bool top = (k == m->n_tiers - 1);
     const bool lp = dt != SRNN_F32;
     const int cur = par, nxt = par ^ 1;
@@ -585,9 +658,8 @@ int tier_tick(Ctx& c, int k, int off, int par) {
         // then [up | gh'] = h [W_up; W_hh]^T + [b_up; b_hh]
         const SrnnTier& u = m->tier[1];
         const int fi = (off / t.n_frame_samples) % u.frame_size;
-        const NoiseJob nz{c.noise, c.seed, c.row0, 0, nullptr, c.step0};    // (the upper tick drew them)
-        const dim3 g2(cdiv(D, 256), cdiv(B, FG_RB));
-        const int planes = 1;
+        const NoiseJob nz = c.noise_job();
+        const dim3 g2(cdiv(D, 256), cdiv(B, FG_RB), 1);
         const int64_t fs0d = (int64_t)t.frame_size * D;
         // [up | gh'] = h [W_up; W_hh]^T + [b_up; b_hh]: its own launch, or inside the
         // persistent launch that follows (c.tick_gemm)
@@ -611,43 +683,35 @@ int tier_tick(Ctx& c, int k, int off, int par) {
             c.gate_done = false;
             return tick_gemm();
         }
-        if (dt == SRNN_F32)
-            hipLaunchKernelGGL((fold_gru_kernel<float>), dim3(g2.x, g2.y, planes), dim3(256), 0,
-                               c.s, c.seq, c.ldseq, c.b.base, off, t.n_frame_samples, c.b.lut2,
-                               c.L, c.b.fmin, c.b.fg + (size_t)fi * 3 * D, c.b.ldg1,
-                               c.b.up[0] + fs0d, c.b.ldup0, c.b.h[0][0][cur], c.b.h[0][0][nxt],
-                               (float*)c.b.hlp[0][0][nxt], B, D, nz);
-        else
-            hipLaunchKernelGGL((fold_gru_kernel<bf16>), dim3(g2.x, g2.y, planes), dim3(256), 0,
-                               c.s, c.seq, c.ldseq, c.b.base, off, t.n_frame_samples, c.b.lut2,
-                               c.L, c.b.fmin, c.b.fg + (size_t)fi * 3 * D, c.b.ldg1,
-                               c.b.up[0] + fs0d, c.b.ldup0, c.b.h[0][0][cur], c.b.h[0][0][nxt],
-                               (bf16*)c.b.hlp[0][0][nxt], B, D, nz);
-        SRNN_LAUNCH_CHECK();
+        RET(gen_typed_launch(dt, [&](auto z) {
+            using T = decltype(z);
+            hipLaunchKernelGGL((fold_gru_kernel<T>), g2, dim3(256), 0, c.s, r.seq, c.ldseq,
+                               c.b.base, off, t.n_frame_samples, c.b.lut2, c.L, c.b.fmin,
+                               c.b.fg + (size_t)fi * 3 * D, c.b.ldg1, c.b.up[0] + fs0d, c.b.ldup0,
+                               c.b.h[0][0][cur], c.b.h[0][0][nxt], (T*)c.b.hlp[0][0][nxt], B, D,
+                               nz);
+        }));
         return tick_gemm();
     }
     if (k == 1 && c.b.fold_top) {
         // folded top tick: a (+ the period's noise) -> gi = a Min1^T + P1, gh1 carried ->
         // [G | gh1'] = h [Wfold; W_hh1]^T + [bfold; b_hh1]
-        NoiseJob nz{c.noise, c.seed, c.row0, 0, nullptr, c.step0};
+        NoiseJob nz = c.noise_job();
         const int gx = cdiv(B, 2);
         int planes = 1;
-        if (c.pl && c.b.lq && env_flag("SRNN_GEN_NOISE_AHEAD", 1)) {
+        if (c.pl && c.b.lq && c.sw.noise_ahead) {
             nz.nsteps = c.b.lq_steps;
             nz.lq = c.b.lq;
             planes = 1 + cdiv(cdiv((int64_t)nz.nsteps * B, 4), gx);
             c.noise_beg = off;
             c.noise_end = off + nz.nsteps;
         }
-        if (dt == SRNN_F32)
-            hipLaunchKernelGGL((tier_a_kernel<float>), dim3(gx, 1, planes), dim3(256), 0, c.s,
-                               c.seq, c.ldseq, c.b.base, off, t.n_frame_samples, c.b.lut2, c.cond,
-                               c.n_cond, m->cond_dim, c.L, t.in_dim, (float*)c.b.atop, B, nz);
-        else
-            hipLaunchKernelGGL((tier_a_kernel<bf16>), dim3(gx, 1, planes), dim3(256), 0, c.s,
-                               c.seq, c.ldseq, c.b.base, off, t.n_frame_samples, c.b.lut2, c.cond,
-                               c.n_cond, m->cond_dim, c.L, t.in_dim, (bf16*)c.b.atop, B, nz);
-        SRNN_LAUNCH_CHECK();
+        RET(gen_typed_launch(dt, [&](auto z) {
+            using T = decltype(z);
+            hipLaunchKernelGGL((tier_a_kernel<T>), dim3(gx, 1, planes), dim3(256), 0, c.s, r.seq,
+                               c.ldseq, c.b.base, off, t.n_frame_samples, c.b.lut2, r.cond,
+                               r.n_cond, m->cond_dim, c.L, t.in_dim, (T*)c.b.atop, B, nz);
+        }));
         const int64_t g0 = (int64_t)t.frame_size * 3 * D;
         RET(srnn_gru_cell_x_impl(dt, B, D, TA_AP, c.b.atop, TA_AP, c.b.min1, nullptr, c.b.p1,
                                  3 * D, c.b.fg + g0, c.b.ldg1, c.b.h[k][0][cur], D,
@@ -661,7 +725,7 @@ int tier_tick(Ctx& c, int k, int off, int par) {
         int64_t ldadd;
         const float* bias;
         if (top) {
-            add = c.row_bias; ldadd = D; bias = nullptr;
+            add = r.row_bias; ldadd = D; bias = nullptr;
         } else {
             const SrnnTier& u = m->tier[k + 1];
             // frame_index = (i // nfs_k) % FS_{k+1}  (model.py:491-492); base is a multiple of L
@@ -671,14 +735,9 @@ int tier_tick(Ctx& c, int k, int off, int par) {
         }
         const size_t tlds = (size_t)(TI_OB + TI_RB) * (t.in_dim | 1) * sizeof(float);
         if (tlds <= 160 * 1024) {
-            // (attribute raised once, to the whole LDS, before the first launch that needs it)
-            if (tlds > 65536)
-                RET(srnn_raise_lds(dt == SRNN_F32 ? (const void*)tier_input_tiled_kernel<float>
-                                                  : (const void*)tier_input_tiled_kernel<bf16>,
-                                   160 * 1024));
-            NoiseJob nz{c.noise, c.seed, c.row0, 0, nullptr, c.step0};
+            NoiseJob nz = c.noise_job();
             int planes = 1;
-            if (k == (c.b.fold ? 1 : 0) && c.pl && c.b.lq && env_flag("SRNN_GEN_NOISE_AHEAD", 1)) {
+            if (k == (c.b.fold ? 1 : 0) && c.pl && c.b.lq && c.sw.noise_ahead) {
                 nz.nsteps = c.b.lq_steps;             // the persistent launches after this tick
                 nz.lq = c.b.lq;
                 const int per = cdiv(D, TI_OB) * cdiv(B, TI_RB);
@@ -687,30 +746,28 @@ int tier_tick(Ctx& c, int k, int off, int par) {
                 c.noise_end = off + nz.nsteps;
             }
             const dim3 grid(cdiv(D, TI_OB), cdiv(B, TI_RB), planes);
-            if (dt == SRNN_F32)
-                hipLaunchKernelGGL((tier_input_tiled_kernel<float>), grid, dim3(256), tlds, c.s,
-                                   c.seq, c.ldseq, c.b.base, off, t.n_frame_samples, c.b.lut2,
-                                   c.cond, c.n_cond, m->cond_dim, c.L, (const float*)t.w_in,
-                                   t.in_dim, bias, add, ldadd, (float*)c.b.x[k], B, D, nz);
-            else
-                hipLaunchKernelGGL((tier_input_tiled_kernel<bf16>), grid, dim3(256), tlds, c.s,
-                                   c.seq, c.ldseq, c.b.base, off, t.n_frame_samples, c.b.lut2,
-                                   c.cond, c.n_cond, m->cond_dim, c.L, (const bf16*)t.w_in,
-                                   t.in_dim, bias, add, ldadd, (bf16*)c.b.x[k], B, D, nz);
+            // (attribute raised once, to the whole LDS, before the first launch that needs it)
+            if (tlds > 65536)
+                RET(srnn_raise_lds(dt == SRNN_F32 ? (const void*)tier_input_tiled_kernel<float>
+                                                  : (const void*)tier_input_tiled_kernel<bf16>,
+                                   160 * 1024));
+            RET(gen_typed_launch(dt, [&](auto z) {
+                using T = decltype(z);
+                hipLaunchKernelGGL((tier_input_tiled_kernel<T>), grid, dim3(256), tlds, c.s, r.seq,
+                                   c.ldseq, c.b.base, off, t.n_frame_samples, c.b.lut2, r.cond,
+                                   r.n_cond, m->cond_dim, c.L, (const T*)t.w_in, t.in_dim, bias,
+                                   add, ldadd, (T*)c.b.x[k], B, D, nz);
+            }));
         } else {
             const size_t lds = (size_t)t.in_dim * sizeof(float);
-            if (dt == SRNN_F32)
-                hipLaunchKernelGGL((tier_input_kernel<float>), dim3(B), dim3(256), lds, c.s,
-                                   c.seq, c.ldseq, c.b.base, off, t.n_frame_samples, c.b.lut2,
-                                   c.cond, c.n_cond, m->cond_dim, c.L, (const float*)t.w_in,
-                                   t.in_dim, bias, add, ldadd, (float*)c.b.x[k], D);
-            else
-                hipLaunchKernelGGL((tier_input_kernel<bf16>), dim3(B), dim3(256), lds, c.s,
-                                   c.seq, c.ldseq, c.b.base, off, t.n_frame_samples, c.b.lut2,
-                                   c.cond, c.n_cond, m->cond_dim, c.L, (const bf16*)t.w_in,
-                                   t.in_dim, bias, add, ldadd, (bf16*)c.b.x[k], D);
+            RET(gen_typed_launch(dt, [&](auto z) {
+                using T = decltype(z);
+                hipLaunchKernelGGL((tier_input_kernel<T>), dim3(B), dim3(256), lds, c.s, r.seq,
+                                   c.ldseq, c.b.base, off, t.n_frame_samples, c.b.lut2, r.cond,
+                                   r.n_cond, m->cond_dim, c.L, (const T*)t.w_in, t.in_dim, bias,
+                                   add, ldadd, (T*)c.b.x[k], D);
+            }));
         }
-        SRNN_LAUNCH_CHECK();
     }
     // 3. GRU layers
     if (k == 1 && c.b.fold) {
@@ -737,24 +794,27 @@ int tier_tick(Ctx& c, int k, int off, int par) {
 }
 
 int mlp_step(Ctx& c, int off) {
-    const SrnnModel* m = c.m;
-    const int D = m->dim, Q = m->q_levels, B = c.B, dt = m->dtype;
+    const GenRequest& r = c.rq;
+    const SrnnModel* m = r.m;
+    const int D = m->dim, Q = m->q_levels, B = r.n_seqs, dt = m->dtype;
     const int FS0 = m->tier[0].frame_size;
-    RET(srnn_mlp_l1_impl(dt, m->tab, c.seq, c.ldseq, off - FS0, c.b.base, B, 1, SRNN_F32,
+    RET(srnn_mlp_l1_impl(dt, m->tab, r.seq, c.ldseq, off - FS0, c.b.base, B, 1, SRNN_F32,
                          c.b.up[0] + (size_t)(off % FS0) * D, c.b.ldup0, c.b.a1, D, D, FS0,
                          Q, c.s));
     RET(linear_fwd(dt, dt, B, D, D, c.b.a1, D, m->w_hid, D, m->b_hid, c.b.a2, D, 1, c.s));
     RET(linear_fwd(dt, SRNN_F32, B, Q, D, c.b.a2, D, m->w_out, D, m->b_out, c.b.logits, Q, 0,
                    c.s));
-    RET(srnn_sample_impl(c.b.logits, Q, B, c.noise, c.seed, c.row0, c.b.base, off, c.L, c.seq, c.ldseq,
-                         c.logp, c.temperature, c.top_k, c.top_p, c.step0, c.n_forced, c.s));
+    RET(srnn_sample_impl(c.b.logits, Q, B, r.noise, r.seed, r.row0, c.b.base, off, c.L, r.seq,
+                         c.ldseq, r.logp, r.temperature, r.top_k, r.top_p, r.step0, r.n_forced,
+                         c.s));
     return 0;
 }
 
 // `periods` consecutive top-tier periods starting at sample *base; tick parity restarts
 // at 0 (callers only chain blocks with an even tick count per tier)
 int run_block(Ctx& c, int periods) {
-    const SrnnModel* m = c.m;
+    const GenRequest& r = c.rq;
+    const SrnnModel* m = r.m;
     int ticks[SRNN_MAX_TIERS] = {0};
     c.noise_end = -1;
     c.gate_done = false;
@@ -774,31 +834,31 @@ int run_block(Ctx& c, int periods) {
             a.w_out = m->w_out; a.b_out = m->b_out;
             a.wfr_hid = c.b.wfr_hid; a.wfr_out = c.b.wfr_out;
             a.up0 = c.b.up[0]; a.ldup = c.b.ldup0;
-            a.noise = c.noise; a.seed = c.seed; a.row0 = c.row0;
-            a.seq = c.seq; a.ldseq = c.ldseq; a.logp = c.logp;
+            a.noise = r.noise; a.seed = r.seed; a.row0 = r.row0;
+            a.seq = r.seq; a.ldseq = c.ldseq; a.logp = r.logp;
             a.base = c.b.base; a.off = off; a.nsteps = m->tier[0].frame_size; a.L = c.L;
-            a.B = c.B; a.D = m->dim; a.FS0 = m->tier[0].frame_size;
+            a.B = r.n_seqs; a.D = m->dim; a.FS0 = m->tier[0].frame_size;
             a.xa1 = c.b.xa1; a.xa2 = c.b.xa2; a.xz = c.b.xz; a.err = c.b.gerr;
             a.census = c.b.gerr + 64;
-            a.temperature = c.temperature; a.top_k = c.top_k; a.top_p = c.top_p;
-            a.step0 = c.step0; a.n_forced = c.n_forced;
+            a.temperature = r.temperature; a.top_k = r.top_k; a.top_p = r.top_p;
+            a.step0 = r.step0; a.n_forced = r.n_forced;
             // (a streamed call on the plain kernels always draws ahead: their in-loop draw,
             //  kept as it was, knows no step origin)
-            if (c.b.lq && (env_flag("SRNN_GEN_NOISE_AHEAD", 1) || (c.step0 != 0 && !c.pl->ctrl))) {
+            if (c.b.lq && (c.sw.noise_ahead || (r.step0 != 0 && !c.pl->ctrl))) {
                 // drawn ahead by a tick's input launch, else by a launch here
                 if (off < c.noise_beg || off + a.nsteps > c.noise_end) {
-                    RET(gen_noise_launch(c.noise, c.seed, c.row0, c.b.base, off, a.nsteps, c.L, c.B,
-                                         c.b.lq, c.step0, c.s));
+                    RET(gen_noise_launch(r.noise, r.seed, r.row0, c.b.base, off, a.nsteps, c.L,
+                                         r.n_seqs, c.b.lq, r.step0, c.s));
                     c.noise_beg = off;
                     c.noise_end = off + a.nsteps;
                 }
-                a.lq = c.b.lq + (size_t)(off - c.noise_beg) * c.B * m->q_levels;
+                a.lq = c.b.lq + (size_t)(off - c.noise_beg) * r.n_seqs * m->q_levels;
             }
             // the next bottom tick's gate update rides at the end of this launch unless an
             // upper tick (new G) comes first
             const int nx = off + m->tier[0].frame_size;
             if (c.b.fold && nx < periods * c.L && nx % m->tier[1].n_frame_samples != 0 &&
-                env_flag("SRNN_GEN_FUSE_GATES", 1)) {
+                c.sw.fuse_gates) {
                 const int fi = (nx / m->tier[0].n_frame_samples) % m->tier[1].frame_size;
                 a.tk = c.b.ticks + 2 * fi + (ticks[0] & 1);    // that tick's G row, cur / nxt
                 c.gate_done = true;
@@ -815,165 +875,62 @@ int run_block(Ctx& c, int periods) {
     return 0;
 }
 
-}  // namespace
-
 // persistent sample loop plan for this model/batch (ok = 0: per-sample kernels)
-static void plan_for(const SrnnModel* m, int n_seqs, int ctrl, GenMlpPlan* pl) {
-    if (!gen_mlp_plan(m->dtype, n_seqs, m->dim, m->tier[0].frame_size, m->q_levels, ctrl, pl) ||
-        !env_flag("SRNN_GEN_PERSIST", 1))
+void plan_for(const SrnnModel* m, int n_seqs, int level, GenMlpPlan* pl, const GenSwitches& sw) {
+    if (!gen_mlp_plan(m->dtype, n_seqs, m->dim, m->tier[0].frame_size, m->q_levels, level, pl) ||
+        !sw.persist)
         pl->ok = 0;
 }
 
-extern "C" int srnn_gen_persistent_rows(int dtype, int n_seqs, int dim, int fs0, int q_levels) {
-    GenMlpPlan pl;
-    if (!gen_mlp_plan(dtype, n_seqs, dim, fs0, q_levels, 0, &pl) || !env_flag("SRNN_GEN_PERSIST", 1))
-        return 0;
-    return pl.R;
-}
-
-// the same for a call with sampling controls: the plan of the controlled instantiations of
-// `level` (1: srnn_generate3 / 4 with temperature or top_k, 64 B more LDS; 2: srnn_generate4
-// with top_p, 96 B more; 0: the plain plan)
-extern "C" int srnn_gen_persistent_rows_level(int dtype, int n_seqs, int dim, int fs0,
-                                              int q_levels, int level) {
-    GenMlpPlan pl;
-    if (level < 0 || level > 2) return 0;
-    if (!gen_mlp_plan(dtype, n_seqs, dim, fs0, q_levels, level, &pl) ||
-        !env_flag("SRNN_GEN_PERSIST", 1))
-        return 0;
-    return pl.R;
-}
-
-extern "C" int srnn_gen_persistent_rows_ctrl(int dtype, int n_seqs, int dim, int fs0,
-                                             int q_levels) {
-    return srnn_gen_persistent_rows_level(dtype, n_seqs, dim, fs0, q_levels, 1);
-}
-
-extern "C" int srnn_gen_workspace_size(const SrnnModel* m, int n_seqs, size_t* bytes) {
-    SRNN_REQUIRE(m && bytes && n_seqs > 0, "gen_workspace_size: bad args");
-    Bufs b;
-    GenMlpPlan pl;
-    plan_for(m, n_seqs, 0, &pl);      // (the workspace does not depend on the controls)
-    *bytes = carve(m, n_seqs, nullptr, &b, &pl);
-    return 0;
-}
-
-extern "C" int srnn_generate4(const SrnnModel* m, int n_seqs, int n_cond, const float* cond,
-                              const float* row_bias, const float* noise, uint64_t seed,
-                              int row0, int64_t* seq, float* logp, void* workspace,
-                              size_t workspace_bytes, int flags, void* stream,
-                              const float* temperature, const int32_t* top_k,
-                              const float* top_p);
-extern "C" int srnn_generate5(const SrnnModel* m, int n_seqs, int n_cond, const float* cond,
-                              const float* row_bias, const float* noise, uint64_t seed,
-                              int row0, int64_t* seq, float* logp, void* workspace,
-                              size_t workspace_bytes, int flags, void* stream,
-                              const float* temperature, const int32_t* top_k,
-                              const float* top_p, const SrnnGenStream* st);
-
 // words of a state record (even: the int64 step count stays 8-byte aligned in every row)
-static int64_t gen_state_row_words(const SrnnModel* m) {
+int64_t gen_state_row_words(const SrnnModel* m, const GenSwitches& sw) {
     const int64_t L = m->tier[m->n_tiers - 1].n_frame_samples;
     const int64_t w = GS_HDR + L + (int64_t)m->n_tiers * m->n_rnn * m->dim +
-                      (fold_ok(m) ? 6 * (int64_t)m->dim : 0);
+                      (fold_ok(m, sw) ? 6 * (int64_t)m->dim : 0);
     return (w + 1) & ~(int64_t)1;
 }
 
-extern "C" size_t srnn_gen_state_bytes(const SrnnModel* m, int n_seqs) {
-    if (!m || n_seqs <= 0 || m->n_tiers < 1 || m->n_tiers > SRNN_MAX_TIERS || m->n_rnn < 1 ||
-        m->n_rnn > SRNN_MAX_RNN || m->dim <= 0)
-        return 0;
-    return (size_t)gen_state_row_words(m) * 4 * (size_t)n_seqs;
-}
+// ---- the phases of a call (gen_run) ------------------------------------------------------
+// gen_validate and gen_prepare depend on (model, n_seqs, control level, switches) and the
+// workspace only -- what a streaming session would keep between chunks; gen_start, gen_blocks
+// and gen_finish are this call's.
 
-extern "C" int srnn_generate(const SrnnModel* m, int n_seqs, int n_cond, const float* cond,
-                             const float* row_bias, const float* noise, uint64_t seed,
-                             int64_t* seq, float* logp, void* workspace, size_t workspace_bytes,
-                             int flags, void* stream) {
-    return srnn_generate4(m, n_seqs, n_cond, cond, row_bias, noise, seed, 0, seq, logp,
-                          workspace, workspace_bytes, flags, stream, nullptr, nullptr, nullptr);
-}
-
-extern "C" int srnn_generate2(const SrnnModel* m, int n_seqs, int n_cond, const float* cond,
-                              const float* row_bias, const float* noise, uint64_t seed,
-                              int row0, int64_t* seq, float* logp, void* workspace,
-                              size_t workspace_bytes, int flags, void* stream) {
-    return srnn_generate4(m, n_seqs, n_cond, cond, row_bias, noise, seed, row0, seq, logp,
-                          workspace, workspace_bytes, flags, stream, nullptr, nullptr, nullptr);
-}
-
-// srnn_generate2 with per-row sampling controls (sampler.hpp sample_row_ctrl): with both
-// arrays null every launch is the plain one; with either, the sampler kernels' controlled
-// instantiations run (the persistent loop's own build, planned and checked as such).
-extern "C" int srnn_generate3(const SrnnModel* m, int n_seqs, int n_cond, const float* cond,
-                              const float* row_bias, const float* noise, uint64_t seed,
-                              int row0, int64_t* seq, float* logp, void* workspace,
-                              size_t workspace_bytes, int flags, void* stream,
-                              const float* temperature, const int32_t* top_k) {
-    return srnn_generate4(m, n_seqs, n_cond, cond, row_bias, noise, seed, row0, seq, logp,
-                          workspace, workspace_bytes, flags, stream, temperature, top_k, nullptr);
-}
-
-// srnn_generate3 with the rows' nucleus mass (sampler.hpp, the (tau, k, p) sample_row_ctrl):
-// top_p given selects the level-2 instantiations, planned and checked as such; top_p null
-// launches exactly what srnn_generate3 launches.
-extern "C" int srnn_generate4(const SrnnModel* m, int n_seqs, int n_cond, const float* cond,
-                              const float* row_bias, const float* noise, uint64_t seed,
-                              int row0, int64_t* seq, float* logp, void* workspace,
-                              size_t workspace_bytes, int flags, void* stream,
-                              const float* temperature, const int32_t* top_k,
-                              const float* top_p) {
-    return srnn_generate5(m, n_seqs, n_cond, cond, row_bias, noise, seed, row0, seq, logp,
-                          workspace, workspace_bytes, flags, stream, temperature, top_k, top_p,
-                          nullptr);
-}
-
-// srnn_generate4 that may start from a carried state (st->state_in), return the one it ends in
-// (st->state_out), draw its Philox noise from step st->step0 on, and keep the rows' first
-// st->n_forced[b] samples as given.  st null or all-default: srnn_generate4's launches.
-extern "C" int srnn_generate5(const SrnnModel* m, int n_seqs, int n_cond, const float* cond,
-                              const float* row_bias, const float* noise, uint64_t seed,
-                              int row0, int64_t* seq, float* logp, void* workspace,
-                              size_t workspace_bytes, int flags, void* stream,
-                              const float* temperature, const int32_t* top_k,
-                              const float* top_p, const SrnnGenStream* st) {
-    const void* state_in = st ? st->state_in : nullptr;
-    void* state_out = st ? st->state_out : nullptr;
-    const uint32_t step0 = st ? st->step0 : 0u;
-    const int* n_forced = st ? st->n_forced : nullptr;
-    SRNN_REQUIRE(row0 >= 0, "generate: negative row offset");
-    SRNN_REQUIRE(m && n_seqs > 0 && n_cond > 0 && seq && workspace, "generate: bad args");
+// Checks the request and lays the call out (plan, workspace, state record).  No HIP work is
+// queued before the last check has passed.
+int gen_validate(Ctx& c) {
+    const GenRequest& r = c.rq;
+    const SrnnModel* m = r.m;
+    SRNN_REQUIRE(r.row0 >= 0, "generate: negative row offset");
+    SRNN_REQUIRE(m && r.n_seqs > 0 && r.n_cond > 0 && r.seq && r.workspace, "generate: bad args");
     SRNN_REQUIRE(m->n_tiers >= 1 && m->n_tiers <= SRNN_MAX_TIERS, "generate: n_tiers");
     SRNN_REQUIRE(m->n_rnn >= 1 && m->n_rnn <= SRNN_MAX_RNN, "generate: n_rnn");
     SRNN_REQUIRE(m->q_levels == 256, "generate: q_levels must be 256");
     SRNN_REQUIRE(m->dim % 16 == 0, "generate: dim must be a multiple of 16");
-    Ctx c;
-    c.m = m;
-    GenMlpPlan pl;
-    plan_for(m, n_seqs, top_p ? 2 : (temperature || top_k || n_forced) ? 1 : 0, &pl);
-    if (flags & 2) pl.ok = 0;          // caller asked for the per-sample kernel path
-    size_t need = carve(m, n_seqs, (char*)workspace, &c.b, &pl);
-    SRNN_REQUIRE(workspace_bytes >= need, "generate: workspace %zu < %zu", workspace_bytes, need);
-    c.B = n_seqs;
-    c.n_cond = n_cond;
+    plan_for(m, r.n_seqs, r.level(), &c.plan, c.sw);
+    if (r.flags & 2) c.plan.ok = 0;          // caller asked for the per-sample kernel path
+    const size_t need = carve(m, r.n_seqs, (char*)r.workspace, &c.b, &c.plan, c.sw);
+    SRNN_REQUIRE(r.workspace_bytes >= need, "generate: workspace %zu < %zu", r.workspace_bytes,
+                 need);
     c.L = m->tier[m->n_tiers - 1].n_frame_samples;
-    const int64_t T = (int64_t)n_cond * c.L;
-    SRNN_REQUIRE((uint64_t)step0 + (uint64_t)T <= 0xFFFFFFFFull,
-                 "generate: step0 %u + %lld steps overflow the 32-bit Philox step counter", step0,
-                 (long long)T);
-    SRNN_REQUIRE(!n_forced || T < (1 << 23), "generate: a forced prefix needs fewer than 2^23 "
-                 "steps per call (%lld)", (long long)T);
-    const int64_t rw = gen_state_row_words(m);
-    SRNN_REQUIRE((!state_in && !state_out) ||
-                     st->state_bytes == (size_t)rw * 4 * (size_t)n_seqs,
+    c.T = (int64_t)r.n_cond * c.L;
+    c.ldseq = (int64_t)c.L * (r.n_cond + 1);
+    SRNN_REQUIRE((uint64_t)r.step0 + (uint64_t)c.T <= 0xFFFFFFFFull,
+                 "generate: step0 %u + %lld steps overflow the 32-bit Philox step counter",
+                 r.step0, (long long)c.T);
+    SRNN_REQUIRE(!r.n_forced || c.T < (1 << 23), "generate: a forced prefix needs fewer than 2^23 "
+                 "steps per call (%lld)", (long long)c.T);
+    c.rw = gen_state_row_words(m, c.sw);
+    const size_t sb = (size_t)c.rw * 4 * (size_t)r.n_seqs;
+    SRNN_REQUIRE((!r.state_in && !r.state_out) || r.state_bytes == sb,
                  "generate: state of %zu bytes, this model / batch / fold layout needs %zu",
-                 st ? st->state_bytes : (size_t)0, (size_t)rw * 4 * (size_t)n_seqs);
-    SRNN_REQUIRE((((uintptr_t)state_in | (uintptr_t)state_out) & 7) == 0,
+                 r.state_bytes, sb);
+    SRNN_REQUIRE((((uintptr_t)r.state_in | (uintptr_t)r.state_out) & 7) == 0,
                  "generate: state buffers must be 8-byte aligned");
-    c.step0 = step0;
-    c.n_forced = n_forced;
-    GenStateMap mp;
-    memset(&mp, 0, sizeof(mp));
+    c.pl = c.plan.ok ? &c.plan : nullptr;
+    c.tick_gemm = c.pl && c.b.fold &&
+                  gen_mlp_tick_gemm_ok(c.pl, (m->tier[0].frame_size + 3) * m->dim, m->dim,
+                                       r.n_seqs);
+    GenStateMap& mp = c.mp;
     mp.L = c.L;
     mp.D = m->dim;
     mp.n_h = m->n_tiers * m->n_rnn;
@@ -984,288 +941,241 @@ extern "C" int srnn_generate5(const SrnnModel* m, int n_seqs, int n_cond, const 
         mp.gh1 = c.b.fg + (size_t)m->tier[1].frame_size * 3 * m->dim;
         mp.ldgh1 = c.b.ldg1;
     }
-    mp.hdr[0] = GS_TAG;
-    mp.hdr[1] = (uint32_t)m->dtype;
-    mp.hdr[2] = (uint32_t)m->n_tiers;
-    mp.hdr[3] = (uint32_t)m->n_rnn;
-    mp.hdr[4] = (uint32_t)m->dim;
-    mp.hdr[5] = (uint32_t)c.L;
-    mp.hdr[6] = (c.b.fold ? 1u : 0u) | (c.b.fold_top ? 2u : 0u);
-    c.cond = cond;
-    c.row_bias = row_bias;
-    c.noise = noise;
-    c.seed = seed;
-    c.row0 = row0;
-    c.seq = seq;
-    c.ldseq = (int64_t)c.L * (n_cond + 1);
-    c.logp = logp;
-    c.temperature = temperature;
-    c.top_k = top_k;
-    c.top_p = top_p;
-    c.pl = pl.ok ? &pl : nullptr;
-    c.tick_gemm = c.pl && c.b.fold &&
-                  gen_mlp_tick_gemm_ok(&pl, (m->tier[0].frame_size + 3) * m->dim, m->dim, n_seqs);
-    hipStream_t user = (hipStream_t)stream;
-    const int D = m->dim, B = n_seqs;
-    // private stream so a hipGraph can be captured regardless of the caller's stream
-    hipStream_t s;
-    SRNN_CHECK_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    hipEvent_t ev;
-    SRNN_CHECK_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    SRNN_CHECK_HIP(hipEventRecord(ev, user));
-    SRNN_CHECK_HIP(hipStreamWaitEvent(s, ev, 0));
-    c.s = s;
-    int rc = 0;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    do {
-        if (state_in) {
-            // every record's header must be one of this call's layout: checked on the host
-            // before anything is launched
-            std::vector<uint32_t> hd((size_t)B * 8);
-            if (hipMemcpy2DAsync(hd.data(), 32, state_in, (size_t)rw * 4, 32, B,
-                                 hipMemcpyDeviceToHost, s) != hipSuccess ||
-                hipStreamSynchronize(s) != hipSuccess) {
-                srnn_set_error("generate: reading the state headers: %s",
-                               hipGetErrorString(hipGetLastError()));
-                rc = 2;
-                break;
-            }
-            for (int b = 0; b < B && !rc; ++b) {
-                const uint32_t* h = hd.data() + (size_t)b * 8;
-                if (memcmp(h, mp.hdr, 32) != 0) {
-                    srnn_set_error(
-                        "generate: state row %d has layout (tag %08x, dtype %u, tiers %u, rnn %u, "
-                        "dim %u, L %u, fold %u), this call needs (tag %08x, dtype %u, tiers %u, "
-                        "rnn %u, dim %u, L %u, fold %u)", b, h[0], h[1], h[2], h[3], h[4], h[5],
-                        h[6], mp.hdr[0], mp.hdr[1], mp.hdr[2], mp.hdr[3], mp.hdr[4], mp.hdr[5],
-                        mp.hdr[6]);
-                    rc = 1;
-                }
-            }
-            if (rc) break;
-        }
-        // 2 * udequantize LUT (bit-exact reference table for mu-law q = 256)
+    const uint32_t hdr[8] = {GS_TAG, (uint32_t)m->dtype, (uint32_t)m->n_tiers, (uint32_t)m->n_rnn,
+                             (uint32_t)m->dim, (uint32_t)c.L,
+                             (c.b.fold ? 1u : 0u) | (c.b.fold_top ? 2u : 0u), 0u};
+    memcpy(mp.hdr, hdr, sizeof(hdr));
+    return 0;
+}
+
+// What the model, the batch size and the plan determine: the 2 x LUT, the persistent loop's
+// weight images, the folded ticks' concatenated and pre-multiplied weights, the tick table.
+int gen_prepare(Ctx& c) {
+    const SrnnModel* m = c.rq.m;
+    const int D = m->dim, dt = m->dtype;
+    const size_t es = dt == SRNN_F32 ? 4 : 2;
+    hipStream_t s = c.s;
+    // 2 * udequantize LUT (bit-exact reference table for mu-law q = 256)
+    float lut2[256];
+    for (int q = 0; q < 256; ++q) {
+        float v;
+        memcpy(&v, &SRNN_ULAW_LUT_BITS[q], 4);
+        lut2[q] = 2.0f * v;
+    }
+    SRNN_CHECK_HIP(hipMemcpyAsync(c.b.lut2, lut2, sizeof(lut2), hipMemcpyHostToDevice, s));
+    if (c.pl)
+        RET(gen_mlp_prep_weights(c.pl, m->w_hid, m->w_out, D, m->q_levels, c.b.wfr_hid,
+                                 c.b.wfr_out, s));
+    std::vector<GenMlpArgs::Tick> tt;
+    if (c.b.fold) {
+        // folded bottom tick operands (see fold_gru_kernel): [W_up; W_hh], [b_up; b_hh]
+        const SrnnTier& t0 = m->tier[0];
+        const SrnnTier& t1 = m->tier[1];
+        const size_t upw = (size_t)t0.frame_size * D;
+        // b_hh (3D floats) to dst, zeros where the layer has none
+        auto copy_bhh = [&](float* dst, const float* b_hh) {
+            return b_hh ? hipMemcpyAsync(dst, b_hh, (size_t)3 * D * 4, hipMemcpyDeviceToDevice, s)
+                        : hipMemsetAsync(dst, 0, (size_t)3 * D * 4, s);
+        };
+        SRNN_CHECK_HIP(hipMemcpyAsync(c.b.wcat, t0.w_up, upw * D * es, hipMemcpyDeviceToDevice, s));
+        SRNN_CHECK_HIP(hipMemcpyAsync((char*)c.b.wcat + upw * D * es, t0.w_hh[0],
+                                      (size_t)3 * D * D * es, hipMemcpyDeviceToDevice, s));
+        SRNN_CHECK_HIP(hipMemcpyAsync(c.b.bcat, t0.b_up, upw * 4, hipMemcpyDeviceToDevice, s));
+        SRNN_CHECK_HIP(copy_bhh(c.b.bcat + upw, t0.b_hh[0]));
+        RET(gen_typed_launch(dt, [&](auto z) {
+            using T = decltype(z);
+            hipLaunchKernelGGL((fold_input_kernel<T>), dim3(cdiv(3 * D, 4)), dim3(256), 0, s,
+                               (const T*)t0.w_ih[0], (const T*)t0.w_in, t0.n_frame_samples,
+                               t0.b_in, t0.b_ih[0], t1.b_up, t1.frame_size, c.b.fmin, c.b.bfold,
+                               3 * D, D);
+        }));
+        // Wfold[j] = W_ih0 (3D x D) . W_up1[j] (D x D, rows j D .. j D + D - 1), bf16 out
         {
-            float lut2[256];
-            for (int q = 0; q < 256; ++q) {
-                float v;
-                memcpy(&v, &SRNN_ULAW_LUT_BITS[q], 4);
-                lut2[q] = 2.0f * v;
-            }
-            rc = hipMemcpyAsync(c.b.lut2, lut2, sizeof(lut2), hipMemcpyHostToDevice, s) ? 2 : 0;
-            if (rc) { srnn_set_error("generate: lut upload"); break; }
-            rc = hipMemsetAsync(c.b.base, 0, 64, s) ? 2 : 0;
-            if (rc) break;
-            if (c.pl) {
-                rc = hipMemsetAsync(c.b.gerr, 0, c.b.gm_bytes, s) ? 2 : 0;
-                if (rc) break;
-                rc = gen_mlp_prep_weights(c.pl, m->w_hid, m->w_out, D, m->q_levels,
-                                          c.b.wfr_hid, c.b.wfr_out, s);
-                if (rc) break;
-            }
-            int L = c.L;
-            rc = hipMemcpyAsync(c.b.base, &L, sizeof(int), hipMemcpyHostToDevice, s) ? 2 : 0;
-            if (rc) break;
-            rc = hipStreamSynchronize(s) ? 2 : 0;   // host staging arrays go out of scope
-            if (rc) break;
+            GemmProblem p;
+            p.dtype = p.out_dtype = dt;
+            p.M = 3 * D; p.N = D; p.K = D; p.batch = t1.frame_size;
+            p.A = t0.w_ih[0]; p.lda = D;
+            p.B = t1.w_up; p.ldb = D; p.sB = (int64_t)D * D;
+            p.C = c.b.wfold; p.ldc = D; p.sC = (int64_t)3 * D * D;
+            RET(srnn_gemm_run(p, s));
         }
-        // initial hidden states: h0 expanded over rows (model.py:224-228)
-        for (int k = 0; k < m->n_tiers && !rc; ++k)
+        // [W_hh1; b_hh1] after the folded rows
+        const size_t g0 = (size_t)t1.frame_size * 3 * D;
+        SRNN_CHECK_HIP(hipMemcpyAsync((char*)c.b.wfold + g0 * D * es, t1.w_hh[0],
+                                      (size_t)3 * D * D * es, hipMemcpyDeviceToDevice, s));
+        SRNN_CHECK_HIP(copy_bhh(c.b.bfold + g0, t1.b_hh[0]));
+        if (c.b.fold_top) {
+            // Min1 = W_ih1 (3D x D) . W_in1 (D x in_dim), zero-padded to TA_AP columns
+            SRNN_CHECK_HIP(hipMemsetAsync(c.b.min1, 0, (size_t)3 * D * TA_AP * es, s));
+            GemmProblem p;
+            p.dtype = p.out_dtype = dt;
+            p.M = 3 * D; p.N = t1.in_dim; p.K = D;
+            p.A = t1.w_ih[0]; p.lda = D;
+            p.B = t1.w_in; p.ldb = t1.in_dim;
+            p.C = c.b.min1; p.ldc = TA_AP;
+            RET(srnn_gemm_run(p, s));
+        }
+        // gate-update operand table of the persistent loop, [fi][cur]
+        tt.resize(2 * t1.frame_size);
+        for (int fi = 0; fi < t1.frame_size; ++fi)
+            for (int pc = 0; pc < 2; ++pc) {
+                GenMlpArgs::Tick& e = tt[2 * fi + pc];
+                e.fmin = c.b.fmin;
+                e.G = c.b.fg + (size_t)fi * 3 * D;
+                e.ldg = c.b.ldg1;
+                e.gh = c.b.up[0] + upw;
+                e.ldgh = c.b.ldup0;
+                e.hp = c.b.h[0][0][pc];
+                e.hn = c.b.h[0][0][pc ^ 1];
+                e.hn_lp = c.b.hlp[0][0][pc ^ 1];
+                e.lut2 = c.b.lut2;
+            }
+        SRNN_CHECK_HIP(hipMemcpyAsync(c.b.ticks, tt.data(), tt.size() * sizeof(tt[0]),
+                                      hipMemcpyHostToDevice, s));
+    }
+    SRNN_CHECK_HIP(hipStreamSynchronize(s));     // the host staging arrays go out of scope
+    return 0;
+}
+
+// This call's start: the block base and the hand-off block, the fresh (or carried) recurrent
+// state, and what follows from it and from row_bias.
+int gen_start(Ctx& c) {
+    const GenRequest& r = c.rq;
+    const SrnnModel* m = r.m;
+    const int D = m->dim, B = r.n_seqs, dt = m->dtype;
+    const bool lp = dt != SRNN_F32;
+    hipStream_t s = c.s;
+    if (r.state_in) {
+        // every record's header must be one of this call's layout: checked on the host before
+        // anything of this call's own is launched
+        std::vector<uint32_t> hd((size_t)B * 8);
+        if (hipMemcpy2DAsync(hd.data(), 32, r.state_in, (size_t)c.rw * 4, 32, B,
+                             hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipStreamSynchronize(s) != hipSuccess) {
+            srnn_set_error("generate: reading the state headers: %s",
+                           hipGetErrorString(hipGetLastError()));
+            return 2;
+        }
+        const uint32_t* w = c.mp.hdr;
+        for (int b = 0; b < B; ++b) {
+            const uint32_t* h = hd.data() + (size_t)b * 8;
+            SRNN_REQUIRE(memcmp(h, w, 32) == 0,
+                         "generate: state row %d has layout (tag %08x, dtype %u, tiers %u, rnn %u, "
+                         "dim %u, L %u, fold %u), this call needs (tag %08x, dtype %u, tiers %u, "
+                         "rnn %u, dim %u, L %u, fold %u)", b, h[0], h[1], h[2], h[3], h[4], h[5],
+                         h[6], w[0], w[1], w[2], w[3], w[4], w[5], w[6]);
+        }
+    }
+    SRNN_CHECK_HIP(hipMemsetAsync(c.b.base, 0, 64, s));
+    if (c.pl) SRNN_CHECK_HIP(hipMemsetAsync(c.b.gerr, 0, c.b.gm_bytes, s));
+    // (from c.L: the context outlives the drain)
+    SRNN_CHECK_HIP(hipMemcpyAsync(c.b.base, &c.L, sizeof(int), hipMemcpyHostToDevice, s));
+    // initial hidden states: h0 expanded over rows (model.py:224-228)
+    for (int k = 0; k < m->n_tiers; ++k)
+        for (int l = 0; l < m->n_rnn; ++l)
+            RET(gen_typed_launch(dt, [&](auto z) {
+                using T = decltype(z);
+                hipLaunchKernelGGL((init_state_kernel<T>), dim3(cdiv(B * D, 256)), dim3(256), 0, s,
+                                   m->tier[k].h0 + (size_t)l * D, c.b.h[k][l][0],
+                                   lp ? (T*)c.b.hlp[k][l][0] : nullptr, B, D);
+            }));
+    if (c.b.fold) {
+        // gh of the folded ticks' first tick, and with the folded top tick
+        // P1 = bf16(row_bias) . W_ih1^T + b_ih1
+        const SrnnTier& t0 = m->tier[0];
+        const SrnnTier& t1 = m->tier[1];
+        RET(linear_fwd(dt, SRNN_F32, B, 3 * D, D, c.b.hlp[1][0][0], D, t1.w_hh[0], D, t1.b_hh[0],
+                       c.mp.gh1, c.b.ldg1, 0, s));
+        if (c.b.fold_top) {
+            RET(gen_typed_launch(dt, [&](auto z) {
+                using T = decltype(z);
+                hipLaunchKernelGGL((copy_cast_kernel<T>), dim3(cdiv(B * D, 256)), dim3(256), 0, s,
+                                   r.row_bias, (T*)c.b.x[1], B * D);
+            }));
+            RET(linear_fwd(dt, SRNN_F32, B, 3 * D, D, c.b.x[1], D, t1.w_ih[0], D, t1.b_ih[0],
+                           c.b.p1, 3 * D, 0, s));
+        }
+        RET(linear_fwd(dt, SRNN_F32, B, 3 * D, D, c.b.hlp[0][0][0], D, t0.w_hh[0], D, t0.b_hh[0],
+                       c.mp.gh0, c.b.ldup0, 0, s));
+    }
+    if (r.state_in) {
+        // the carried state replaces the fresh start's: buffer [0] of every h (and its T
+        // copy), the folded ticks' gh rows and the sample history seq[:, 0:L)
+        GenStateMap mp = c.mp;
+        for (int k = 0; k < m->n_tiers; ++k)
             for (int l = 0; l < m->n_rnn; ++l) {
-                const float* h0 = m->tier[k].h0 + (size_t)l * D;
-                if (m->dtype == SRNN_F32)
-                    hipLaunchKernelGGL((init_state_kernel<float>), dim3(cdiv(B * D, 256)),
-                                       dim3(256), 0, s, h0, c.b.h[k][l][0], (float*)nullptr, B, D);
-                else
-                    hipLaunchKernelGGL((init_state_kernel<bf16>), dim3(cdiv(B * D, 256)),
-                                       dim3(256), 0, s, h0, c.b.h[k][l][0],
-                                       (bf16*)c.b.hlp[k][l][0], B, D);
+                mp.h[k * m->n_rnn + l] = c.b.h[k][l][0];
+                mp.hlp[k * m->n_rnn + l] = lp ? c.b.hlp[k][l][0] : nullptr;
             }
-        if (!rc && c.b.fold) {
-            // folded bottom tick operands (see fold_gru_kernel), and gh of its first tick
-            const SrnnTier& t0 = m->tier[0];
-            const size_t upw = (size_t)t0.frame_size * D;
-            const size_t es = m->dtype == SRNN_F32 ? 4 : 2;
-            rc = (hipMemcpyAsync(c.b.wcat, t0.w_up, upw * D * es, hipMemcpyDeviceToDevice, s) ||
-                  hipMemcpyAsync((char*)c.b.wcat + upw * D * es, t0.w_hh[0], (size_t)3 * D * D * es,
-                                 hipMemcpyDeviceToDevice, s) ||
-                  hipMemcpyAsync(c.b.bcat, t0.b_up, upw * 4, hipMemcpyDeviceToDevice, s))
-                     ? 2 : 0;
-            if (!rc)
-                rc = (t0.b_hh[0] ? hipMemcpyAsync(c.b.bcat + upw, t0.b_hh[0], (size_t)3 * D * 4,
-                                                  hipMemcpyDeviceToDevice, s)
-                                 : hipMemsetAsync(c.b.bcat + upw, 0, (size_t)3 * D * 4, s))
-                         ? 2 : 0;
-            if (rc) { srnn_set_error("generate: fold weight copy"); break; }
-            const SrnnTier& t1 = m->tier[1];
-            if (m->dtype == SRNN_F32)
-                hipLaunchKernelGGL((fold_input_kernel<float>), dim3(cdiv(3 * D, 4)), dim3(256), 0,
-                                   s, (const float*)t0.w_ih[0], (const float*)t0.w_in,
-                                   t0.n_frame_samples, t0.b_in, t0.b_ih[0], t1.b_up,
-                                   t1.frame_size, c.b.fmin, c.b.bfold, 3 * D, D);
-            else
-                hipLaunchKernelGGL((fold_input_kernel<bf16>), dim3(cdiv(3 * D, 4)), dim3(256), 0,
-                                   s, (const bf16*)t0.w_ih[0], (const bf16*)t0.w_in,
-                                   t0.n_frame_samples, t0.b_in, t0.b_ih[0], t1.b_up,
-                                   t1.frame_size, c.b.fmin, c.b.bfold, 3 * D, D);
-            if (hipGetLastError() != hipSuccess) {
-                srnn_set_error("generate: fold_input launch");
-                rc = 2;
-                break;
-            }
-            // Wfold[j] = W_ih0 (3D x D) . W_up1[j] (D x D, rows j D .. j D + D - 1), bf16 out
-            {
-                GemmProblem p;
-                p.dtype = p.out_dtype = m->dtype;
-                p.M = 3 * D; p.N = D; p.K = D; p.batch = t1.frame_size;
-                p.A = t0.w_ih[0]; p.lda = D;
-                p.B = t1.w_up; p.ldb = D; p.sB = (int64_t)D * D;
-                p.C = c.b.wfold; p.ldc = D; p.sC = (int64_t)3 * D * D;
-                rc = srnn_gemm_run(p, s);
-            }
-            if (rc) break;
-            // [W_hh1; b_hh1] after the folded rows, and gh1 of the first upper tick
-            const size_t g0 = (size_t)t1.frame_size * 3 * D;
-            rc = (hipMemcpyAsync((char*)c.b.wfold + g0 * D * es, t1.w_hh[0], (size_t)3 * D * D * es,
-                                 hipMemcpyDeviceToDevice, s) ||
-                  (t1.b_hh[0] ? hipMemcpyAsync(c.b.bfold + g0, t1.b_hh[0], (size_t)3 * D * 4,
-                                               hipMemcpyDeviceToDevice, s)
-                              : hipMemsetAsync(c.b.bfold + g0, 0, (size_t)3 * D * 4, s)))
-                     ? 2 : 0;
-            if (rc) { srnn_set_error("generate: fold weight copy"); break; }
-            rc = linear_fwd(m->dtype, SRNN_F32, B, 3 * D, D, c.b.hlp[1][0][0], D, t1.w_hh[0], D,
-                            t1.b_hh[0], c.b.fg + g0, c.b.ldg1, 0, s);
-            if (rc) break;
-            // gate-update operand table of the persistent loop, [fi][cur]
-            std::vector<GenMlpArgs::Tick> tt(2 * t1.frame_size);
-            for (int fi = 0; fi < t1.frame_size; ++fi)
-                for (int pc = 0; pc < 2; ++pc) {
-                    GenMlpArgs::Tick& e = tt[2 * fi + pc];
-                    e.fmin = c.b.fmin;
-                    e.G = c.b.fg + (size_t)fi * 3 * D;
-                    e.ldg = c.b.ldg1;
-                    e.gh = c.b.up[0] + upw;
-                    e.ldgh = c.b.ldup0;
-                    e.hp = c.b.h[0][0][pc];
-                    e.hn = c.b.h[0][0][pc ^ 1];
-                    e.hn_lp = c.b.hlp[0][0][pc ^ 1];
-                    e.lut2 = c.b.lut2;
-                }
-            rc = (hipMemcpyAsync(c.b.ticks, tt.data(), tt.size() * sizeof(tt[0]),
-                                 hipMemcpyHostToDevice, s) || hipStreamSynchronize(s)) ? 2 : 0;
-            if (rc) { srnn_set_error("generate: tick table upload"); break; }
-            if (c.b.fold_top) {
-                // Min1 = W_ih1 (3D x D) . W_in1 (D x in_dim), zero-padded to TA_AP columns;
-                // P1 = bf16(row_bias) . W_ih1^T + b_ih1
-                rc = hipMemsetAsync(c.b.min1, 0, (size_t)3 * D * TA_AP * es, s) ? 2 : 0;
-                if (!rc) {
-                    GemmProblem p;
-                    p.dtype = p.out_dtype = m->dtype;
-                    p.M = 3 * D; p.N = t1.in_dim; p.K = D;
-                    p.A = t1.w_ih[0]; p.lda = D;
-                    p.B = t1.w_in; p.ldb = t1.in_dim;
-                    p.C = c.b.min1; p.ldc = TA_AP;
-                    rc = srnn_gemm_run(p, s);
-                }
-                if (!rc) {
-                    if (m->dtype == SRNN_F32)
-                        hipLaunchKernelGGL((copy_cast_kernel<float>), dim3(cdiv(B * D, 256)),
-                                           dim3(256), 0, s, c.row_bias, (float*)c.b.x[1], B * D);
-                    else
-                        hipLaunchKernelGGL((copy_cast_kernel<bf16>), dim3(cdiv(B * D, 256)),
-                                           dim3(256), 0, s, c.row_bias, (bf16*)c.b.x[1], B * D);
-                    rc = linear_fwd(m->dtype, SRNN_F32, B, 3 * D, D, c.b.x[1], D, t1.w_ih[0], D,
-                                    t1.b_ih[0], c.b.p1, 3 * D, 0, s);
-                }
-                if (rc) break;
-            }
-            rc = linear_fwd(m->dtype, SRNN_F32, B, 3 * D, D, c.b.hlp[0][0][0], D, t0.w_hh[0], D,
-                            t0.b_hh[0], c.b.up[0] + upw, c.b.ldup0, 0, s);
+        RET(gen_typed_launch(dt, [&](auto z) {
+            using T = decltype(z);
+            hipLaunchKernelGGL((gen_state_unpack_kernel<T>), dim3(cdiv(c.rw, 256), B), dim3(256),
+                               0, s, (const uint32_t*)r.state_in, c.rw, mp, r.seq, c.ldseq);
+        }));
+    }
+    return 0;
+}
+
+// The blocks of two top-tier periods -- the first eagerly, the rest as replays of one captured
+// block when asked for (flags & 1) -- and the odd period at the end.
+int gen_blocks(Ctx& c) {
+    const int nblocks = c.rq.n_cond / 2;
+    int done = 0;
+    if (nblocks > 0) {
+        // first block eagerly: it raises the per-kernel attributes, outside any capture
+        RET(run_block(c, 2));
+        done = 1;
+    }
+    if ((c.rq.flags & 1) && nblocks > 1) {
+        if (hipStreamBeginCapture(c.s, hipStreamCaptureModeThreadLocal) != hipSuccess) {
+            srnn_set_error("generate: begin capture failed");
+            return 2;
         }
-        if (rc) break;
-        if (state_in) {
-            // the carried state replaces the fresh start's: buffer [0] of every h (and its T
-            // copy), the folded ticks' gh rows and the sample history seq[:, 0:L)
-            const bool lp = m->dtype != SRNN_F32;
-            for (int k = 0; k < m->n_tiers; ++k)
-                for (int l = 0; l < m->n_rnn; ++l) {
-                    mp.h[k * m->n_rnn + l] = c.b.h[k][l][0];
-                    mp.hlp[k * m->n_rnn + l] = lp ? c.b.hlp[k][l][0] : nullptr;
-                }
-            const dim3 grid(cdiv(rw, 256), B);
-            if (lp)
-                hipLaunchKernelGGL((gen_state_unpack_kernel<bf16>), grid, dim3(256), 0, s,
-                                   (const uint32_t*)state_in, rw, mp, seq, c.ldseq);
-            else
-                hipLaunchKernelGGL((gen_state_unpack_kernel<float>), grid, dim3(256), 0, s,
-                                   (const uint32_t*)state_in, rw, mp, seq, c.ldseq);
-            if (hipGetLastError() != hipSuccess) {
-                srnn_set_error("generate: state unpack launch");
-                rc = 2;
-                break;
-            }
+        // (the capture is ended after a failed block too: the stream must leave capture mode)
+        const int rc = run_block(c, 2);
+        const hipError_t ce = hipStreamEndCapture(c.s, &c.gs.graph);
+        RET(rc);
+        if (ce != hipSuccess ||
+            hipGraphInstantiate(&c.gs.exec, c.gs.graph, nullptr, nullptr, 0) != hipSuccess) {
+            srnn_set_error("generate: graph capture/instantiate failed");
+            return 2;
         }
-        const bool use_graph = (flags & 1) != 0;
-        int done = 0;
-        const int nblocks = n_cond / 2;
-        if (nblocks > 0) {
-            // first block eagerly (also warms up per-kernel attributes)
-            rc = run_block(c, 2);
-            if (rc) break;
-            done = 1;
-            if (use_graph && nblocks > 1) {
-                if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-                    srnn_set_error("generate: begin capture failed");
-                    rc = 2;
-                    break;
-                }
-                rc = run_block(c, 2);
-                hipError_t ce = hipStreamEndCapture(s, &graph);
-                if (rc) break;
-                if (ce != hipSuccess || hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) !=
-                                            hipSuccess) {
-                    srnn_set_error("generate: graph capture/instantiate failed");
-                    rc = 2;
-                    break;
-                }
-                for (; done < nblocks; ++done) {
-                    if (hipGraphLaunch(exec, s) != hipSuccess) {
-                        srnn_set_error("generate: graph launch failed");
-                        rc = 2;
-                        break;
-                    }
-                }
-                if (rc) break;
-            } else {
-                for (; done < nblocks && !rc; ++done) rc = run_block(c, 2);
-                if (rc) break;
+        for (; done < nblocks; ++done)
+            if (hipGraphLaunch(c.gs.exec, c.s) != hipSuccess) {
+                srnn_set_error("generate: graph launch failed");
+                return 2;
             }
+    }
+    for (; done < nblocks; ++done) RET(run_block(c, 2));
+    if (c.rq.n_cond % 2) RET(run_block(c, 1));
+    return 0;
+}
+
+// Runs whatever the earlier phases returned (rc): packs the end state of a call that got
+// through, drains the private stream before its resources go (generation is one long call),
+// and reads the persistent loop's error word.
+int gen_finish(Ctx& c, int rc) {
+    const GenRequest& r = c.rq;
+    const SrnnModel* m = r.m;
+    if (!rc && r.state_out) {
+        // tick parity restarts at 0 in every block and the two-period blocks tick every tier
+        // an even number of times, so only a trailing one-period block moves a tier's live h:
+        // to buffer [1] where the tier ticks an odd number of times per period (the top tier
+        // always does)
+        GenStateMap mp = c.mp;
+        for (int k = 0; k < m->n_tiers; ++k) {
+            const int live = (r.n_cond % 2) ? (c.L / m->tier[k].n_frame_samples) & 1 : 0;
+            for (int l = 0; l < m->n_rnn; ++l) mp.h[k * m->n_rnn + l] = c.b.h[k][l][live];
         }
-        if (n_cond % 2) rc = run_block(c, 1);
-        if (!rc && state_out) {
-            // tick parity restarts at 0 in every block and the two-period blocks tick every tier
-            // an even number of times, so only a trailing one-period block moves a tier's live h:
-            // to buffer [1] where the tier ticks an odd number of times per period (the top tier
-            // always does)
-            for (int k = 0; k < m->n_tiers; ++k) {
-                const int live = (n_cond % 2) ? (c.L / m->tier[k].n_frame_samples) & 1 : 0;
-                for (int l = 0; l < m->n_rnn; ++l) {
-                    mp.h[k * m->n_rnn + l] = c.b.h[k][l][live];
-                    mp.hlp[k * m->n_rnn + l] = nullptr;
-                }
-            }
-            hipLaunchKernelGGL(gen_state_pack_kernel, dim3(cdiv(rw, 256), B), dim3(256), 0, s,
-                               (uint32_t*)state_out, (const uint32_t*)state_in, rw, mp, seq,
-                               c.ldseq, T);
-            if (hipGetLastError() != hipSuccess) {
-                srnn_set_error("generate: state pack launch");
-                rc = 2;
-            }
+        hipLaunchKernelGGL(gen_state_pack_kernel, dim3(cdiv(c.rw, 256), r.n_seqs), dim3(256), 0,
+                           c.s, (uint32_t*)r.state_out, (const uint32_t*)r.state_in, c.rw, mp,
+                           r.seq, c.ldseq, c.T);
+        if (hipGetLastError() != hipSuccess) {
+            srnn_set_error("generate: state pack launch");
+            rc = 2;
         }
-    } while (0);
-    // the private stream is drained before its resources go (generation is one long call)
-    if (hipStreamSynchronize(s) != hipSuccess && !rc) {
+    }
+    if (hipStreamSynchronize(c.s) != hipSuccess && !rc) {
         srnn_set_error("generate: %s", hipGetErrorString(hipGetLastError()));
         rc = 2;
     }
@@ -1278,9 +1188,115 @@ extern "C" int srnn_generate5(const SrnnModel* m, int n_seqs, int n_cond, const 
             rc = 2;
         }
     }
-    if (exec) (void)hipGraphExecDestroy(exec);
-    if (graph) (void)hipGraphDestroy(graph);
-    (void)hipEventDestroy(ev);
-    (void)hipStreamDestroy(s);
     return rc;
+}
+
+int gen_run(const GenRequest& rq) {
+    Ctx c{rq, GenSwitches::read()};
+    RET(gen_validate(c));
+    RET(c.gs.open(rq.stream));
+    c.s = c.gs.s;
+    int rc = gen_prepare(c);
+    if (!rc) rc = gen_start(c);
+    if (!rc) rc = gen_blocks(c);
+    return gen_finish(c, rc);
+}
+
+}  // namespace
+
+// rows per group of the persistent sample loop at sampling-control level `level` (0: the plain
+// plan; 1: temperature / top_k / a forced prefix, 64 B more LDS; 2: with top_p, 96 B more), or
+// 0 where the call would run the per-sample kernels
+extern "C" int srnn_gen_persistent_rows_level(int dtype, int n_seqs, int dim, int fs0,
+                                              int q_levels, int level) {
+    GenMlpPlan pl;
+    if (level < 0 || level > 2) return 0;
+    if (!gen_mlp_plan(dtype, n_seqs, dim, fs0, q_levels, level, &pl) ||
+        !GenSwitches::read().persist)
+        return 0;
+    return pl.R;
+}
+
+extern "C" int srnn_gen_persistent_rows(int dtype, int n_seqs, int dim, int fs0, int q_levels) {
+    return srnn_gen_persistent_rows_level(dtype, n_seqs, dim, fs0, q_levels, 0);
+}
+
+extern "C" int srnn_gen_persistent_rows_ctrl(int dtype, int n_seqs, int dim, int fs0,
+                                             int q_levels) {
+    return srnn_gen_persistent_rows_level(dtype, n_seqs, dim, fs0, q_levels, 1);
+}
+
+extern "C" int srnn_gen_workspace_size(const SrnnModel* m, int n_seqs, size_t* bytes) {
+    SRNN_REQUIRE(m && bytes && n_seqs > 0, "gen_workspace_size: bad args");
+    const GenSwitches sw = GenSwitches::read();
+    Bufs b;
+    GenMlpPlan pl;
+    plan_for(m, n_seqs, 0, &pl, sw);      // (the workspace does not depend on the controls)
+    *bytes = carve(m, n_seqs, nullptr, &b, &pl, sw);
+    return 0;
+}
+
+extern "C" size_t srnn_gen_state_bytes(const SrnnModel* m, int n_seqs) {
+    if (!m || n_seqs <= 0 || m->n_tiers < 1 || m->n_tiers > SRNN_MAX_TIERS || m->n_rnn < 1 ||
+        m->n_rnn > SRNN_MAX_RNN || m->dim <= 0)
+        return 0;
+    return (size_t)gen_state_row_words(m, GenSwitches::read()) * 4 * (size_t)n_seqs;
+}
+
+// The five generations of the entry point (include/samplernn_hip.h states each): all fill one
+// request, in its field order, and run it.
+extern "C" int srnn_generate(const SrnnModel* m, int n_seqs, int n_cond, const float* cond,
+                             const float* row_bias, const float* noise, uint64_t seed,
+                             int64_t* seq, float* logp, void* workspace, size_t workspace_bytes,
+                             int flags, void* stream) {
+    return gen_run({m, n_seqs, n_cond, cond, row_bias, noise, seed, 0, seq, logp, workspace,
+                    workspace_bytes, flags, (hipStream_t)stream});
+}
+
+extern "C" int srnn_generate2(const SrnnModel* m, int n_seqs, int n_cond, const float* cond,
+                              const float* row_bias, const float* noise, uint64_t seed,
+                              int row0, int64_t* seq, float* logp, void* workspace,
+                              size_t workspace_bytes, int flags, void* stream) {
+    return gen_run({m, n_seqs, n_cond, cond, row_bias, noise, seed, row0, seq, logp, workspace,
+                    workspace_bytes, flags, (hipStream_t)stream});
+}
+
+// with per-row sampling controls (sampler.hpp sample_row_ctrl): with both arrays null every
+// launch is the plain one; with either, the sampler kernels' controlled instantiations run
+// (the persistent loop's own build, planned and checked as such)
+extern "C" int srnn_generate3(const SrnnModel* m, int n_seqs, int n_cond, const float* cond,
+                              const float* row_bias, const float* noise, uint64_t seed,
+                              int row0, int64_t* seq, float* logp, void* workspace,
+                              size_t workspace_bytes, int flags, void* stream,
+                              const float* temperature, const int32_t* top_k) {
+    return gen_run({m, n_seqs, n_cond, cond, row_bias, noise, seed, row0, seq, logp, workspace,
+                    workspace_bytes, flags, (hipStream_t)stream, temperature, top_k});
+}
+
+// with the rows' nucleus mass (sampler.hpp, the (tau, k, p) sample_row_ctrl): top_p given
+// selects the level-2 instantiations; top_p null launches exactly what srnn_generate3 launches
+extern "C" int srnn_generate4(const SrnnModel* m, int n_seqs, int n_cond, const float* cond,
+                              const float* row_bias, const float* noise, uint64_t seed,
+                              int row0, int64_t* seq, float* logp, void* workspace,
+                              size_t workspace_bytes, int flags, void* stream,
+                              const float* temperature, const int32_t* top_k,
+                              const float* top_p) {
+    return gen_run({m, n_seqs, n_cond, cond, row_bias, noise, seed, row0, seq, logp, workspace,
+                    workspace_bytes, flags, (hipStream_t)stream, temperature, top_k, top_p});
+}
+
+// that may start from a carried state (st->state_in), return the one it ends in
+// (st->state_out), draw its Philox noise from step st->step0 on, and keep the rows' first
+// st->n_forced[b] samples as given.  st null or all-default: srnn_generate4's launches.
+extern "C" int srnn_generate5(const SrnnModel* m, int n_seqs, int n_cond, const float* cond,
+                              const float* row_bias, const float* noise, uint64_t seed,
+                              int row0, int64_t* seq, float* logp, void* workspace,
+                              size_t workspace_bytes, int flags, void* stream,
+                              const float* temperature, const int32_t* top_k,
+                              const float* top_p, const SrnnGenStream* st) {
+    static const SrnnGenStream none{};
+    if (!st) st = &none;
+    return gen_run({m, n_seqs, n_cond, cond, row_bias, noise, seed, row0, seq, logp, workspace,
+                    workspace_bytes, flags, (hipStream_t)stream, temperature, top_k, top_p,
+                    st->state_in, st->state_out, st->state_bytes, st->step0, st->n_forced});
 }

@@ -658,8 +658,8 @@ int srnn_sample_impl(const float* z, int64_t ldz, int B, const float* noise, uin
                      int row0, const int* base, int off, int L, int64_t* seq, int64_t ldseq,
                      float* logp_out, const float* temperature, const int* top_k,
                      const float* top_p, uint32_t step0, const int* n_forced, hipStream_t s) {
-    auto k = top_p ? sample_kernel<2> : (temperature || top_k || n_forced) ? sample_kernel<1>
-                                                                            : sample_kernel<0>;
+    const int lv = sample_ctrl_level(temperature, top_k, top_p, n_forced);
+    auto k = lv == 2 ? sample_kernel<2> : lv == 1 ? sample_kernel<1> : sample_kernel<0>;
     hipLaunchKernelGGL(k, dim3(cdiv(B, 4)), dim3(256), 0, s, z, ldz, B, noise, seed, row0, base,
                        off, L, seq, ldseq, logp_out, temperature, top_k, top_p, step0, n_forced);
     SRNN_LAUNCH_CHECK();
@@ -695,8 +695,9 @@ extern "C" int srnn_sample_rows(const float* logits, int64_t ld, int rows, const
                  "sample_rows: logits rows must be 16-byte aligned (ld %lld)", (long long)ld);
     SRNN_REQUIRE(((uintptr_t)noise & 15) == 0, "sample_rows: noise must be 16-byte aligned");
     SRNN_REQUIRE(row0 >= 0 && step >= 0, "sample_rows: negative row offset or step");
-    auto k = top_p ? sample_rows_kernel<2> : (temperature || top_k) ? sample_rows_kernel<1>
-                                                                    : sample_rows_kernel<0>;
+    const int lv = sample_ctrl_level(temperature, top_k, top_p);
+    auto k = lv == 2 ? sample_rows_kernel<2> : lv == 1 ? sample_rows_kernel<1>
+                                                       : sample_rows_kernel<0>;
     hipLaunchKernelGGL(k, dim3(cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, logits, ld, rows,
                        noise, seed, row0, step, index, logp, temperature, top_k, top_p);
     SRNN_LAUNCH_CHECK();

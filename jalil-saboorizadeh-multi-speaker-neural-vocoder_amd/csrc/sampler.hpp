@@ -325,3 +325,12 @@ __device__ __forceinline__ int sample_row_ctrl(const floatx4& v, const floatx4& 
     if (logp_row) row_logp(z, logp_row, lane);
     return bi;
 }
+
+// The level of a call's sampling controls, from the arrays it was given: 2 with top_p, 1 with
+// temperature, top_k or a forced prefix (n_forced: the controlled builds keep it), else 0.
+// The one definition: it picks the samplers' instantiation (CT), the persistent loop's plan
+// and its launch check.
+inline int sample_ctrl_level(const void* temperature, const void* top_k, const void* top_p,
+                             const void* n_forced = nullptr) {
+    return top_p ? 2 : (temperature || top_k || n_forced) ? 1 : 0;
+}

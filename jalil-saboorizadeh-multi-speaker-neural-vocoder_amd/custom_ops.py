@@ -402,7 +402,12 @@ def _(dstep):
 
 # ------------------------------------------------------------------ generation
 def _generate(weights, meta, cond, row_bias, noise, seed, row_offset, flags, return_logp,
-              temperature=None, top_k=None, top_p=None):
+              temperature=None, top_k=None, top_p=None, state=None, step0=0, prefix=None,
+              n_forced=None, return_state=False):
+    """The one path into the library's generation (srnn_generate5), behind the four registered
+    ops, which check their arguments first: allocates seq (q_zero history, the prefix written
+    in), logp, the end state and the workspace, fills SrnnGenStream and calls.  Everything at
+    its default launches the plain kernels.  Returns (seq, logp, end state or empty)."""
     import ctypes
     import model
     m = model.srnn_model_struct(weights, meta)
@@ -412,20 +417,29 @@ def _generate(weights, meta, cond, row_bias, noise, seed, row_offset, flags, ret
     Q = m.q_levels
     dev = cond.device
     seq = torch.full((n_seqs, L + T), Q // 2, dtype=torch.long, device=dev)   # q_zero
+    if prefix is not None:
+        seq[:, L:L + prefix.shape[1]] = prefix.clamp(0, Q - 1)
     logp = torch.empty((T, n_seqs, Q), device=dev) if return_logp else torch.empty(0, device=dev)
+    st = H.SrnnGenStream()
+    st.step0 = int(step0)
+    st.n_forced = H.ptr(n_forced)
+    row_bytes = int(H.lib().dll.srnn_gen_state_bytes(ctypes.byref(m), 1)) if return_state else 0
+    out_state = torch.empty((n_seqs, row_bytes) if return_state else (0,), dtype=torch.uint8,
+                            device=dev)
+    if return_state:
+        st.state_out = H.ptr(out_state)
+        st.state_bytes = out_state.numel()
+    if state is not None:
+        st.state_in = H.ptr(state)
+        st.state_bytes = state.numel()
     sz = ctypes.c_size_t(0)
     H.lib().call('srnn_gen_workspace_size', ctypes.byref(m), n_seqs, ctypes.byref(sz))
     ws = torch.empty(sz.value, device=dev, dtype=torch.uint8)
-    args = (ctypes.byref(m), n_seqs, num_cond, H.ptr(cond), H.ptr(row_bias), H.ptr(noise),
-            int(seed) & ((1 << 64) - 1), int(row_offset), H.ptr(seq),
-            H.ptr(logp) if return_logp else None, H.ptr(ws), sz.value, int(flags), H.stream())
-    if top_p is not None:
-        H.lib().call('srnn_generate4', *args, H.ptr(temperature), H.ptr(top_k), H.ptr(top_p))
-    elif temperature is None and top_k is None:
-        H.lib().call('srnn_generate2', *args)
-    else:
-        H.lib().call('srnn_generate3', *args, H.ptr(temperature), H.ptr(top_k))
-    return seq, logp
+    H.lib().call('srnn_generate5', ctypes.byref(m), n_seqs, num_cond, H.ptr(cond),
+                 H.ptr(row_bias), H.ptr(noise), int(seed) & ((1 << 64) - 1), int(row_offset),
+                 H.ptr(seq), H.ptr(logp) if return_logp else None, H.ptr(ws), sz.value, int(flags),
+                 H.stream(), H.ptr(temperature), H.ptr(top_k), H.ptr(top_p), ctypes.byref(st))
+    return seq, logp, out_state
 
 
 def _generate_fake(meta, cond, return_logp):
@@ -444,7 +458,8 @@ def generate(weights: list[Tensor], meta: list[int], cond: Tensor, row_bias: Ten
     """The whole autoregressive loop (model.py:445-520) on the device: (sample indices
     (n_seqs, L + T) int64, per-step log-probs (T, n_seqs, Q) or empty).  weights / meta:
     model.generation_weights' tensors and layout."""
-    return _generate(weights, meta, cond, row_bias, noise, seed, row_offset, flags, return_logp)
+    return _generate(weights, meta, cond, row_bias, noise, seed, row_offset, flags,
+                     return_logp)[:2]
 
 
 @generate.register_fake
@@ -471,7 +486,7 @@ def generate_ctrl(weights: list[Tensor], meta: list[int], cond: Tensor, row_bias
     _check_rows('generate_ctrl', cond.shape[0], cond.device,
                 ('temperature', temperature, torch.float32), ('top_k', top_k, torch.int32))
     return _generate(weights, meta, cond, row_bias, noise, seed, row_offset, flags, return_logp,
-                     temperature, top_k)
+                     temperature, top_k)[:2]
 
 
 @generate_ctrl.register_fake
@@ -493,7 +508,7 @@ def generate_ctrl_p(weights: list[Tensor], meta: list[int], cond: Tensor, row_bi
                 ('temperature', temperature, torch.float32), ('top_k', top_k, torch.int32),
                 ('top_p', top_p, torch.float32))
     return _generate(weights, meta, cond, row_bias, noise, seed, row_offset, flags, return_logp,
-                     temperature, top_k, top_p)
+                     temperature, top_k, top_p)[:2]
 
 
 @generate_ctrl_p.register_fake
@@ -539,10 +554,8 @@ def generate_stream(weights: list[Tensor], meta: list[int], cond: Tensor, row_bi
                   None = P for every row
       return_state  also return the state the call ends in, else an empty tensor
     Returns (seq (n_seqs, L + T) int64, logp (T, n_seqs, Q) or empty, state)."""
-    import ctypes
-    import model
-    n_seqs, num_cond = cond.shape[0], cond.shape[1]
-    dev = cond.device
+    n_seqs, dev = cond.shape[0], cond.device
+    T = cond.shape[1] * meta[-1]            # steps of the call (meta: _generate_fake)
     ctl = [(n, t, dt) for n, t, dt in (('temperature', temperature, torch.float32),
                                        ('top_k', top_k, torch.int32),
                                        ('top_p', top_p, torch.float32)) if t is not None]
@@ -551,14 +564,9 @@ def generate_stream(weights: list[Tensor], meta: list[int], cond: Tensor, row_bi
             raise ValueError('generate_stream: prefix_len without a prefix')
         ctl.append(('prefix_len', prefix_len, torch.int32))
     _check_rows('generate_stream', n_seqs, dev, *ctl)
-    m = model.srnn_model_struct(weights, meta)
-    L = m.tier[m.n_tiers - 1].n_frame_samples
-    T = num_cond * L
-    Q = m.q_levels
     if step0 < 0 or step0 + T > 0xFFFFFFFF:
         raise ValueError('generate_stream: step0 %d + %d steps do not fit the 32-bit counter'
                          % (step0, T))
-    seq = torch.full((n_seqs, L + T), Q // 2, dtype=torch.long, device=dev)   # q_zero
     n_forced = None
     if prefix is not None:
         if (prefix.dim() != 2 or prefix.shape[0] != n_seqs or prefix.shape[1] > T or
@@ -566,36 +574,16 @@ def generate_stream(weights: list[Tensor], meta: list[int], cond: Tensor, row_bi
             raise ValueError('generate_stream: prefix must be an (n_seqs, <= %d) int64 tensor '
                              'on %s' % (T, dev))
         P = prefix.shape[1]
-        seq[:, L:L + P] = prefix.clamp(0, Q - 1)
         n_forced = (prefix_len.clamp(0, P) if prefix_len is not None else
                     torch.full((n_seqs,), P, dtype=torch.int32, device=dev)).contiguous()
-    row_bytes = int(H.lib().dll.srnn_gen_state_bytes(ctypes.byref(m), 1))
-    st = H.SrnnGenStream()
-    st.step0 = int(step0)
-    st.n_forced = H.ptr(n_forced)
     if state is not None:
         if (state.dtype != torch.uint8 or state.dim() != 2 or state.shape[0] != n_seqs or
                 state.device != dev):
             raise ValueError('generate_stream: state must be an (n_seqs, row_bytes) uint8 tensor '
                              'on %s' % dev)
         state = state.contiguous()
-        st.state_in = H.ptr(state)
-        st.state_bytes = state.numel()
-    out_state = torch.empty((n_seqs, row_bytes) if return_state else (0,), dtype=torch.uint8,
-                            device=dev)
-    if return_state:
-        st.state_out = H.ptr(out_state)
-        if state is None:
-            st.state_bytes = out_state.numel()
-    logp = torch.empty((T, n_seqs, Q), device=dev) if return_logp else torch.empty(0, device=dev)
-    sz = ctypes.c_size_t(0)
-    H.lib().call('srnn_gen_workspace_size', ctypes.byref(m), n_seqs, ctypes.byref(sz))
-    ws = torch.empty(sz.value, device=dev, dtype=torch.uint8)
-    H.lib().call('srnn_generate5', ctypes.byref(m), n_seqs, num_cond, H.ptr(cond),
-                 H.ptr(row_bias), H.ptr(noise), int(seed) & ((1 << 64) - 1), int(row_offset),
-                 H.ptr(seq), H.ptr(logp) if return_logp else None, H.ptr(ws), sz.value, int(flags),
-                 H.stream(), H.ptr(temperature), H.ptr(top_k), H.ptr(top_p), ctypes.byref(st))
-    return seq, logp, out_state
+    return _generate(weights, meta, cond, row_bias, noise, seed, row_offset, flags, return_logp,
+                     temperature, top_k, top_p, state, step0, prefix, n_forced, return_state)
 
 
 @generate_stream.register_fake

@@ -417,15 +417,10 @@ def gen_persistent_rows(dtype, n_seqs, dim, fs0, q_levels=256, ctrl=False):
     level = int(ctrl)
     if level not in (0, 1, 2):
         raise ValueError('gen_persistent_rows: ctrl must be False, True, 1 or 2')
-    if level == 2:
-        fn = lib().dll.srnn_gen_persistent_rows_level
-        fn.argtypes = [_I, _I, _I, _I, _I, _I]
-        fn.restype = _I
-        return int(fn(dcode(dtype), n_seqs, dim, fs0, q_levels, 2))
-    fn = lib().dll.srnn_gen_persistent_rows_ctrl if level else lib().dll.srnn_gen_persistent_rows
-    fn.argtypes = [_I, _I, _I, _I, _I]
+    fn = lib().dll.srnn_gen_persistent_rows_level
+    fn.argtypes = [_I, _I, _I, _I, _I, _I]
     fn.restype = _I
-    return int(fn(dcode(dtype), n_seqs, dim, fs0, q_levels))
+    return int(fn(dcode(dtype), n_seqs, dim, fs0, q_levels, level))
 
 
 def sample_rows(logits, noise=None, seed=0, row0=0, step=0, temperature=None, top_k=None,
