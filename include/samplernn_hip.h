@@ -591,6 +591,44 @@ int srnn_generate5(const SrnnModel* m, int n_seqs, int n_cond, const float* cond
                    void* stream, const float* temperature, const int32_t* top_k,
                    const float* top_p, const SrnnGenStream* st);
 
+typedef struct SrnnGenRows {
+    const int32_t*  noise_row;  /* device (n_seqs) or NULL: Philox row of local row b       */
+    const uint32_t* step0;      /* device (n_seqs) or NULL: Philox step of row b's sample 0  */
+} SrnnGenRows;
+
+/* srnn_generate5 whose rows may each have their own Philox origin, so that a stream keeps its
+ * noise whichever local row serves it and whatever the other rows' step counts are (continuous
+ * batching: rows of one call at different points of different utterances).  With rows NULL, or
+ * both of its fields NULL, it is exactly srnn_generate5 (same kernels).
+ *   noise_row  the Philox row of local row b is noise_row[b] in place of row0 + b.  Every value
+ *              must be >= 0, else return code 1 and a message, before anything is written.
+ *              Equal values are allowed: such rows draw the same noise.
+ *   step0      the Philox step of row b's sample t is step0[b] + t; st->step0 is then ignored.
+ *              step0[b] + n_cond * L must fit 32 bits for every row, else return code 1 and a
+ *              message, before anything is written.
+ * Both arrays only move Philox counters: a replayed `noise` buffer and `logp` keep their index
+ * from the call's own first step and the call's own row b, and with `noise` given the arrays are
+ * not read.  The arrays are read on the host once (the call synchronises `stream` first) and by
+ * the launches that draw noise; a call with either array draws every launch's noise ahead of the
+ * persistent sample loop (as SRNN_GEN_NOISE_AHEAD=1 does, whatever that switch says), because
+ * the loop's own draw knows no per-row origin.                                               */
+int srnn_generate6(const SrnnModel* m, int n_seqs, int n_cond, const float* cond,
+                   const float* row_bias, const float* noise, uint64_t seed, int row0,
+                   int64_t* seq, float* logp, void* workspace, size_t workspace_bytes, int flags,
+                   void* stream, const float* temperature, const int32_t* top_k,
+                   const float* top_p, const SrnnGenStream* st, const SrnnGenRows* rows);
+
+/* Writes to state_out (device, state_bytes = srnn_gen_state_bytes(m, n_seqs), 8-byte aligned)
+ * the records of n_seqs rows that have done no step: this process's header, step count 0, a
+ * q_zero history (q_levels / 2), h0 of every tier and layer and, with folded ticks, their carried
+ * products exactly as a fresh start of n_seqs rows computes them.  A srnn_generate5 / 6 call of
+ * n_seqs rows with state_in set to these records equals the call with state_in = NULL bit for
+ * bit -- indices, log-probs and state_out -- and all n_seqs records are equal, so any of them
+ * may start a new stream in a row of a call whose other rows are mid-stream.  workspace: as for
+ * srnn_generate (srnn_gen_workspace_size(m, n_seqs)).  Synchronises before it returns.         */
+int srnn_gen_state_fresh(const SrnnModel* m, int n_seqs, void* state_out, size_t state_bytes,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

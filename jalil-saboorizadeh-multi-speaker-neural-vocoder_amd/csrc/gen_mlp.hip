@@ -1225,7 +1225,7 @@ int gen_mlp_tick_gemm_ok(const GenMlpPlan* pl, int N, int K, int B) {
            cdiv(N / 16, nblk) <= gmt::TMAX && B <= 128 && nblk <= 2048 - gmt::WORDS;
 }
 
-int gen_mlp_launch(const GenMlpPlan* pl, GenMlpArgs a, hipStream_t s) {
+int gen_mlp_launch(const GenMlpPlan* pl, GenMlpArgs a, bool row_origins, hipStream_t s) {
     SRNN_REQUIRE(pl && pl->ok, "gen_mlp: no plan");
     a.R = pl->R;
     a.G = pl->G;
@@ -1255,6 +1255,9 @@ int gen_mlp_launch(const GenMlpPlan* pl, GenMlpArgs a, hipStream_t s) {
     }
     SRNN_REQUIRE(pl->ctrl != 0 || a.step0 == 0 || a.lq,
                  "gen_mlp: the plain loop's own draw has no step origin (noise must be drawn ahead)");
+    // (no build of the loop reads per-row origins: the launches that draw ahead apply them)
+    SRNN_REQUIRE(!row_origins || a.lq,
+                 "gen_mlp: the loop's own draw has no per-row origins (noise must be drawn ahead)");
     const bool tg = a.tg.N > 0;
     if (tg) {
         SRNN_REQUIRE(pl->kernel_tg && a.wfr_hid && a.wfr_out,

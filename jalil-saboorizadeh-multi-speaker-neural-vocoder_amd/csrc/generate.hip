@@ -26,6 +26,12 @@ int srnn_sample_impl(const float* z, int64_t ldz, int B, const float* noise, uin
                      const int* base, int off, int L, int64_t* seq, int64_t ldseq,
                      float* logp_out, const float* temperature, const int* top_k,
                      const float* top_p, uint32_t step0, const int* n_forced, hipStream_t s);
+int srnn_sample_origin_impl(const float* z, int64_t ldz, int B, const float* noise,
+                            uint64_t seed, int row0, const int* base, int off, int L,
+                            int64_t* seq, int64_t ldseq, float* logp_out,
+                            const float* temperature, const int* top_k, const float* top_p,
+                            uint32_t step0, const int* n_forced, const int* noise_row,
+                            const uint32_t* row_step0, hipStream_t s);
 int srnn_gru_cell_impl(int dtype, int B, int D, int Din, const void* x, int64_t ldx,
                        const void* wih, const float* bih, const float* gi, int64_t ldgi,
                        const void* h, int64_t ldh, const float* hf, int64_t ldhf, const void* whh,
@@ -86,6 +92,8 @@ struct NoiseJob {
     int nsteps;              // 0: no noise work
     float* lq;               // (nsteps, B, Q)
     uint32_t step0;          // Philox step of the call's first sample (streaming)
+    const int* noise_row;    // per-row Philox origins (sampler.hpp sample_noise), or null
+    const uint32_t* row_step0;
 };
 
 // noise plane z >= 1 of a 256-thread launch: one wave per (step, row)
@@ -98,7 +106,8 @@ __device__ __forceinline__ void noise_plane(const NoiseJob& nz, const int* base,
     const int st = idx / B, b = idx - st * B;
     const int i = *base + off + st;
     *reinterpret_cast<floatx4*>(nz.lq + ((int64_t)st * B + b) * 256 + 4 * lane) =
-        log_noise(sample_noise(nz.noise, nz.seed, B, b, i - L, lane, nz.row0, nz.step0));
+        log_noise(sample_noise(nz.noise, nz.seed, B, b, i - L, lane, nz.row0, nz.step0,
+                               nz.noise_row, nz.row_step0));
 }
 
 constexpr int TI_RB = 8, TI_OB = 64;
@@ -343,6 +352,7 @@ struct GenStateMap {
     float* gh1;
     int64_t ldgh1;
     uint32_t hdr[8];                            // words [0, 8) of a record of this call
+    uint32_t q_zero;                            // the history of a fresh record (pack, no seq)
 };
 
 // grid (words of a record / 256, B): word w of row b
@@ -396,7 +406,8 @@ __global__ __launch_bounds__(256) void gen_state_pack_kernel(
     const int D = mp.D;
     uint32_t v = 0u;
     if (w < mp.L) {
-        v = (uint32_t)seq[(int64_t)b * ldseq + (ldseq - mp.L) + w];
+        // (no seq: the q_zero history of a stream that has done no step)
+        v = seq ? (uint32_t)seq[(int64_t)b * ldseq + (ldseq - mp.L) + w] : mp.q_zero;
     } else if (w - mp.L < (int64_t)mp.n_h * D) {
         const int64_t e = w - mp.L;
         const int j = (int)(e / D), u = (int)(e - (int64_t)j * D);
@@ -576,6 +587,9 @@ struct GenRequest {
     size_t state_bytes = 0;
     uint32_t step0 = 0;                   // Philox step of sample L (steps done before the call)
     const int* n_forced = nullptr;        // per-row forced prefix lengths (device), or null
+    const int* noise_row = nullptr;       // per-row Philox row (device, n_seqs), or null: row0 + b
+    const uint32_t* row_step0 = nullptr;  // per-row Philox step origin (device), or null: step0
+    bool row_origins() const { return noise_row || row_step0; }
     int level() const { return sample_ctrl_level(temperature, top_k, top_p, n_forced); }
 };
 
@@ -619,6 +633,7 @@ struct GenStream {
 struct Ctx {
     const GenRequest& rq;
     const GenSwitches sw;
+    const bool fresh = false; // srnn_gen_state_fresh: the start of a call and its record, no step
     GenStream gs;
     Bufs b{};
     int L = 0;                // the top tier's period
@@ -639,7 +654,9 @@ struct Ctx {
     GenMlpArgs::TickGemm pending{};
     GenStateMap mp{};         // the call's state record layout (header, gh rows; h per use)
     // a launch's noise source, drawing nothing ahead (the upper tick drew them) until given lq
-    NoiseJob noise_job() const { return {rq.noise, rq.seed, rq.row0, 0, nullptr, rq.step0}; }
+    NoiseJob noise_job() const {
+        return {rq.noise, rq.seed, rq.row0, 0, nullptr, rq.step0, rq.noise_row, rq.row_step0};
+    }
 };
 
 #define RET(x) do { int _r = (x); if (_r) return _r; } while (0)
@@ -804,6 +821,11 @@ int mlp_step(Ctx& c, int off) {
     RET(linear_fwd(dt, dt, B, D, D, c.b.a1, D, m->w_hid, D, m->b_hid, c.b.a2, D, 1, c.s));
     RET(linear_fwd(dt, SRNN_F32, B, Q, D, c.b.a2, D, m->w_out, D, m->b_out, c.b.logits, Q, 0,
                    c.s));
+    if (r.row_origins())
+        return srnn_sample_origin_impl(c.b.logits, Q, B, r.noise, r.seed, r.row0, c.b.base, off,
+                                       c.L, r.seq, c.ldseq, r.logp, r.temperature, r.top_k,
+                                       r.top_p, r.step0, r.n_forced, r.noise_row, r.row_step0,
+                                       c.s);
     RET(srnn_sample_impl(c.b.logits, Q, B, r.noise, r.seed, r.row0, c.b.base, off, c.L, r.seq,
                          c.ldseq, r.logp, r.temperature, r.top_k, r.top_p, r.step0, r.n_forced,
                          c.s));
@@ -843,12 +865,18 @@ int run_block(Ctx& c, int periods) {
             a.temperature = r.temperature; a.top_k = r.top_k; a.top_p = r.top_p;
             a.step0 = r.step0; a.n_forced = r.n_forced;
             // (a streamed call on the plain kernels always draws ahead: their in-loop draw,
-            //  kept as it was, knows no step origin)
-            if (c.b.lq && (c.sw.noise_ahead || (r.step0 != 0 && !c.pl->ctrl))) {
+            //  kept as it was, knows no step origin; nor does any build's know per-row origins)
+            if (c.b.lq && (c.sw.noise_ahead || (r.step0 != 0 && !c.pl->ctrl) ||
+                           r.row_origins())) {
                 // drawn ahead by a tick's input launch, else by a launch here
                 if (off < c.noise_beg || off + a.nsteps > c.noise_end) {
-                    RET(gen_noise_launch(r.noise, r.seed, r.row0, c.b.base, off, a.nsteps, c.L,
-                                         r.n_seqs, c.b.lq, r.step0, c.s));
+                    if (r.row_origins())
+                        RET(gen_noise_origin_launch(r.noise, r.seed, r.row0, c.b.base, off,
+                                                    a.nsteps, c.L, r.n_seqs, c.b.lq, r.step0,
+                                                    r.noise_row, r.row_step0, c.s));
+                    else
+                        RET(gen_noise_launch(r.noise, r.seed, r.row0, c.b.base, off, a.nsteps,
+                                             c.L, r.n_seqs, c.b.lq, r.step0, c.s));
                     c.noise_beg = off;
                     c.noise_end = off + a.nsteps;
                 }
@@ -867,7 +895,7 @@ int run_block(Ctx& c, int periods) {
                 a.tg = c.pending;
                 c.pending = GenMlpArgs::TickGemm{};
             }
-            RET(gen_mlp_launch(c.pl, a, c.s));
+            RET(gen_mlp_launch(c.pl, a, r.row_origins(), c.s));
         }
     }
     hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(1), 0, c.s, c.b.base, periods * c.L);
@@ -895,13 +923,45 @@ int64_t gen_state_row_words(const SrnnModel* m, const GenSwitches& sw) {
 // workspace only -- what a streaming session would keep between chunks; gen_start, gen_blocks
 // and gen_finish are this call's.
 
+// The rows' own Philox origins, read back (the only HIP call of the validation, and it queues
+// nothing): a row below 0 or a step counter that would wrap within the call is refused.
+int gen_validate_rows(Ctx& c) {
+    const GenRequest& r = c.rq;
+    if (!r.row_origins() || r.noise) return 0;   // (replayed noise: the arrays move no counter)
+    const size_t B = (size_t)r.n_seqs;
+    std::vector<uint32_t> v(B);
+    auto read = [&](const void* src, const char* what) -> int {
+        if (hipStreamSynchronize(r.stream) != hipSuccess ||
+            hipMemcpy(v.data(), src, B * 4, hipMemcpyDeviceToHost) != hipSuccess) {
+            srnn_set_error("generate: reading %s: %s", what, hipGetErrorString(hipGetLastError()));
+            return 2;
+        }
+        return 0;
+    };
+    if (r.noise_row) {
+        RET(read(r.noise_row, "noise_row"));
+        for (size_t b = 0; b < B; ++b)
+            SRNN_REQUIRE((int32_t)v[b] >= 0, "generate: noise_row[%zu] = %d is negative", b,
+                         (int32_t)v[b]);
+    }
+    if (r.row_step0) {
+        RET(read(r.row_step0, "the rows' step0"));
+        for (size_t b = 0; b < B; ++b)
+            SRNN_REQUIRE((uint64_t)v[b] + (uint64_t)c.T <= 0xFFFFFFFFull,
+                         "generate: row %zu: step0 %u + %lld steps overflow the 32-bit Philox step "
+                         "counter", b, v[b], (long long)c.T);
+    }
+    return 0;
+}
+
 // Checks the request and lays the call out (plan, workspace, state record).  No HIP work is
 // queued before the last check has passed.
 int gen_validate(Ctx& c) {
     const GenRequest& r = c.rq;
     const SrnnModel* m = r.m;
     SRNN_REQUIRE(r.row0 >= 0, "generate: negative row offset");
-    SRNN_REQUIRE(m && r.n_seqs > 0 && r.n_cond > 0 && r.seq && r.workspace, "generate: bad args");
+    SRNN_REQUIRE(m && r.n_seqs > 0 && r.n_cond > 0 && (r.seq || c.fresh) && r.workspace,
+                 "generate: bad args");
     SRNN_REQUIRE(m->n_tiers >= 1 && m->n_tiers <= SRNN_MAX_TIERS, "generate: n_tiers");
     SRNN_REQUIRE(m->n_rnn >= 1 && m->n_rnn <= SRNN_MAX_RNN, "generate: n_rnn");
     SRNN_REQUIRE(m->q_levels == 256, "generate: q_levels must be 256");
@@ -912,7 +972,7 @@ int gen_validate(Ctx& c) {
     SRNN_REQUIRE(r.workspace_bytes >= need, "generate: workspace %zu < %zu", r.workspace_bytes,
                  need);
     c.L = m->tier[m->n_tiers - 1].n_frame_samples;
-    c.T = (int64_t)r.n_cond * c.L;
+    c.T = c.fresh ? 0 : (int64_t)r.n_cond * c.L;
     c.ldseq = (int64_t)c.L * (r.n_cond + 1);
     SRNN_REQUIRE((uint64_t)r.step0 + (uint64_t)c.T <= 0xFFFFFFFFull,
                  "generate: step0 %u + %lld steps overflow the 32-bit Philox step counter",
@@ -945,7 +1005,8 @@ int gen_validate(Ctx& c) {
                              (uint32_t)m->dim, (uint32_t)c.L,
                              (c.b.fold ? 1u : 0u) | (c.b.fold_top ? 2u : 0u), 0u};
     memcpy(mp.hdr, hdr, sizeof(hdr));
-    return 0;
+    mp.q_zero = (uint32_t)(m->q_levels / 2);
+    return gen_validate_rows(c);
 }
 
 // What the model, the batch size and the plan determine: the 2 x LUT, the persistent loop's
@@ -1037,6 +1098,34 @@ int gen_prepare(Ctx& c) {
     return 0;
 }
 
+// The recurrent state of rows that have done no step, in buffer [0]: h0 of every tier and layer
+// and, with folded ticks, the gh rows of their first tick.  A call's fresh start, and all of a
+// fresh record (srnn_gen_state_fresh) but its q_zero history.
+int gen_init_state(Ctx& c) {
+    const SrnnModel* m = c.rq.m;
+    const int D = m->dim, B = c.rq.n_seqs, dt = m->dtype;
+    const bool lp = dt != SRNN_F32;
+    hipStream_t s = c.s;
+    // initial hidden states: h0 expanded over rows (model.py:224-228)
+    for (int k = 0; k < m->n_tiers; ++k)
+        for (int l = 0; l < m->n_rnn; ++l)
+            RET(gen_typed_launch(dt, [&](auto z) {
+                using T = decltype(z);
+                hipLaunchKernelGGL((init_state_kernel<T>), dim3(cdiv(B * D, 256)), dim3(256), 0, s,
+                                   m->tier[k].h0 + (size_t)l * D, c.b.h[k][l][0],
+                                   lp ? (T*)c.b.hlp[k][l][0] : nullptr, B, D);
+            }));
+    if (c.b.fold) {
+        const SrnnTier& t0 = m->tier[0];
+        const SrnnTier& t1 = m->tier[1];
+        RET(linear_fwd(dt, SRNN_F32, B, 3 * D, D, c.b.hlp[1][0][0], D, t1.w_hh[0], D, t1.b_hh[0],
+                       c.mp.gh1, c.b.ldg1, 0, s));
+        RET(linear_fwd(dt, SRNN_F32, B, 3 * D, D, c.b.hlp[0][0][0], D, t0.w_hh[0], D, t0.b_hh[0],
+                       c.mp.gh0, c.b.ldup0, 0, s));
+    }
+    return 0;
+}
+
 // This call's start: the block base and the hand-off block, the fresh (or carried) recurrent
 // state, and what follows from it and from row_bias.
 int gen_start(Ctx& c) {
@@ -1070,33 +1159,17 @@ int gen_start(Ctx& c) {
     if (c.pl) SRNN_CHECK_HIP(hipMemsetAsync(c.b.gerr, 0, c.b.gm_bytes, s));
     // (from c.L: the context outlives the drain)
     SRNN_CHECK_HIP(hipMemcpyAsync(c.b.base, &c.L, sizeof(int), hipMemcpyHostToDevice, s));
-    // initial hidden states: h0 expanded over rows (model.py:224-228)
-    for (int k = 0; k < m->n_tiers; ++k)
-        for (int l = 0; l < m->n_rnn; ++l)
-            RET(gen_typed_launch(dt, [&](auto z) {
-                using T = decltype(z);
-                hipLaunchKernelGGL((init_state_kernel<T>), dim3(cdiv(B * D, 256)), dim3(256), 0, s,
-                                   m->tier[k].h0 + (size_t)l * D, c.b.h[k][l][0],
-                                   lp ? (T*)c.b.hlp[k][l][0] : nullptr, B, D);
-            }));
-    if (c.b.fold) {
-        // gh of the folded ticks' first tick, and with the folded top tick
-        // P1 = bf16(row_bias) . W_ih1^T + b_ih1
-        const SrnnTier& t0 = m->tier[0];
+    RET(gen_init_state(c));
+    if (c.b.fold_top) {
+        // with the folded top tick P1 = bf16(row_bias) . W_ih1^T + b_ih1
         const SrnnTier& t1 = m->tier[1];
-        RET(linear_fwd(dt, SRNN_F32, B, 3 * D, D, c.b.hlp[1][0][0], D, t1.w_hh[0], D, t1.b_hh[0],
-                       c.mp.gh1, c.b.ldg1, 0, s));
-        if (c.b.fold_top) {
-            RET(gen_typed_launch(dt, [&](auto z) {
-                using T = decltype(z);
-                hipLaunchKernelGGL((copy_cast_kernel<T>), dim3(cdiv(B * D, 256)), dim3(256), 0, s,
-                                   r.row_bias, (T*)c.b.x[1], B * D);
-            }));
-            RET(linear_fwd(dt, SRNN_F32, B, 3 * D, D, c.b.x[1], D, t1.w_ih[0], D, t1.b_ih[0],
-                           c.b.p1, 3 * D, 0, s));
-        }
-        RET(linear_fwd(dt, SRNN_F32, B, 3 * D, D, c.b.hlp[0][0][0], D, t0.w_hh[0], D, t0.b_hh[0],
-                       c.mp.gh0, c.b.ldup0, 0, s));
+        RET(gen_typed_launch(dt, [&](auto z) {
+            using T = decltype(z);
+            hipLaunchKernelGGL((copy_cast_kernel<T>), dim3(cdiv(B * D, 256)), dim3(256), 0, s,
+                               r.row_bias, (T*)c.b.x[1], B * D);
+        }));
+        RET(linear_fwd(dt, SRNN_F32, B, 3 * D, D, c.b.x[1], D, t1.w_ih[0], D, t1.b_ih[0], c.b.p1,
+                       3 * D, 0, s));
     }
     if (r.state_in) {
         // the carried state replaces the fresh start's: buffer [0] of every h (and its T
@@ -1164,12 +1237,13 @@ int gen_finish(Ctx& c, int rc) {
         // always does)
         GenStateMap mp = c.mp;
         for (int k = 0; k < m->n_tiers; ++k) {
-            const int live = (r.n_cond % 2) ? (c.L / m->tier[k].n_frame_samples) & 1 : 0;
+            const int live =
+                (!c.fresh && r.n_cond % 2) ? (c.L / m->tier[k].n_frame_samples) & 1 : 0;
             for (int l = 0; l < m->n_rnn; ++l) mp.h[k * m->n_rnn + l] = c.b.h[k][l][live];
         }
         hipLaunchKernelGGL(gen_state_pack_kernel, dim3(cdiv(c.rw, 256), r.n_seqs), dim3(256), 0,
                            c.s, (uint32_t*)r.state_out, (const uint32_t*)r.state_in, c.rw, mp,
-                           r.seq, c.ldseq, c.T);
+                           c.fresh ? nullptr : r.seq, c.ldseq, c.T);
         if (hipGetLastError() != hipSuccess) {
             srnn_set_error("generate: state pack launch");
             rc = 2;
@@ -1179,7 +1253,7 @@ int gen_finish(Ctx& c, int rc) {
         srnn_set_error("generate: %s", hipGetErrorString(hipGetLastError()));
         rc = 2;
     }
-    if (!rc && c.pl) {
+    if (!rc && c.pl && !c.fresh) {
         int e = 0;
         if (hipMemcpy(&e, c.b.gerr, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess || e) {
             srnn_set_error(e == 2 ? "generate: persistent sample loop's workgroups were not all "
@@ -1199,6 +1273,19 @@ int gen_run(const GenRequest& rq) {
     int rc = gen_prepare(c);
     if (!rc) rc = gen_start(c);
     if (!rc) rc = gen_blocks(c);
+    return gen_finish(c, rc);
+}
+
+// srnn_gen_state_fresh: a call's phases up to its fresh start, then its end: the pack of T = 0
+// steps, from no sample history
+int gen_fresh(const GenRequest& rq) {
+    Ctx c{rq, GenSwitches::read(), true};
+    SRNN_REQUIRE(rq.state_out, "gen_state_fresh: bad args");
+    RET(gen_validate(c));
+    RET(c.gs.open(rq.stream));
+    c.s = c.gs.s;
+    int rc = gen_prepare(c);
+    if (!rc) rc = gen_init_state(c);
     return gen_finish(c, rc);
 }
 
@@ -1243,7 +1330,7 @@ extern "C" size_t srnn_gen_state_bytes(const SrnnModel* m, int n_seqs) {
     return (size_t)gen_state_row_words(m, GenSwitches::read()) * 4 * (size_t)n_seqs;
 }
 
-// The five generations of the entry point (include/samplernn_hip.h states each): all fill one
+// The six generations of the entry point (include/samplernn_hip.h states each): all fill one
 // request, in its field order, and run it.
 extern "C" int srnn_generate(const SrnnModel* m, int n_seqs, int n_cond, const float* cond,
                              const float* row_bias, const float* noise, uint64_t seed,
@@ -1294,9 +1381,39 @@ extern "C" int srnn_generate5(const SrnnModel* m, int n_seqs, int n_cond, const 
                               size_t workspace_bytes, int flags, void* stream,
                               const float* temperature, const int32_t* top_k,
                               const float* top_p, const SrnnGenStream* st) {
+    return srnn_generate6(m, n_seqs, n_cond, cond, row_bias, noise, seed, row0, seq, logp,
+                          workspace, workspace_bytes, flags, stream, temperature, top_k, top_p, st,
+                          nullptr);
+}
+
+// with the rows' own Philox origins (sampler.hpp sample_noise): rows->noise_row[b] in place of
+// row0 + b, rows->step0[b] in place of st->step0.  rows null or both fields null:
+// srnn_generate5's launches.
+extern "C" int srnn_generate6(const SrnnModel* m, int n_seqs, int n_cond, const float* cond,
+                              const float* row_bias, const float* noise, uint64_t seed,
+                              int row0, int64_t* seq, float* logp, void* workspace,
+                              size_t workspace_bytes, int flags, void* stream,
+                              const float* temperature, const int32_t* top_k,
+                              const float* top_p, const SrnnGenStream* st,
+                              const SrnnGenRows* rows) {
     static const SrnnGenStream none{};
+    static const SrnnGenRows norows{};
     if (!st) st = &none;
+    if (!rows) rows = &norows;
     return gen_run({m, n_seqs, n_cond, cond, row_bias, noise, seed, row0, seq, logp, workspace,
                     workspace_bytes, flags, (hipStream_t)stream, temperature, top_k, top_p,
-                    st->state_in, st->state_out, st->state_bytes, st->step0, st->n_forced});
+                    st->state_in, st->state_out, st->state_bytes, rows->step0 ? 0u : st->step0,
+                    st->n_forced, rows->noise_row, rows->step0});
+}
+
+// n_seqs records of a stream that has done no step, as a fresh start of n_seqs rows computes
+// them: a call from them is the call with state_in = NULL, bit for bit
+extern "C" int srnn_gen_state_fresh(const SrnnModel* m, int n_seqs, void* state_out,
+                                    size_t state_bytes, void* workspace, size_t workspace_bytes,
+                                    void* stream) {
+    GenRequest rq{m, n_seqs, 1, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, workspace,
+                  workspace_bytes, 0, (hipStream_t)stream};
+    rq.state_out = state_out;
+    rq.state_bytes = state_bytes;
+    return gen_fresh(rq);
 }

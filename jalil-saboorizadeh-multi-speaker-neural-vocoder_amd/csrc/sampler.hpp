@@ -88,12 +88,21 @@ __device__ __forceinline__ float exp1_from_u32(uint32_t x) {
 // larger batch (rank-sharded generation) draws exactly the single-process stream.
 // `step` is relative to the call (the index into a replayed noise buffer); the Philox counter
 // is step0 + step, step0 the steps the stream had completed before the call (streaming:
-// srnn_generate5).
+// srnn_generate5).  Per-row origins (srnn_generate6, continuous batching): noise_row[b] replaces
+// row0 + b and row_step0[b] replaces step0, so a stream keeps its draws whichever local row
+// serves it and whatever the other rows' step counts are.  Both only move Philox counters: a
+// replayed buffer keeps its call-relative index.  Null (the default): the counters above.
 __device__ __forceinline__ floatx4 sample_noise(const float* noise, uint64_t seed, int B, int b,
                                                 int step, int lane, int row0 = 0,
-                                                uint32_t step0 = 0u) {
+                                                uint32_t step0 = 0u,
+                                                const int* noise_row = nullptr,
+                                                const uint32_t* row_step0 = nullptr) {
     if (noise)
         return *reinterpret_cast<const floatx4*>(noise + ((int64_t)step * B + b) * 256 + 4 * lane);
+    // (the origins are moved, the expression below is not touched: with the arrays null at
+    //  compile time a caller's code is what it was without them)
+    if (noise_row) row0 = noise_row[b] - b;
+    if (row_step0) step0 = row_step0[b];
     const uint4 rnd = philox4x32(make_uint4((uint32_t)lane, (uint32_t)(row0 + b),
                                             (uint32_t)step + step0, 0u),
                                  make_uint2((uint32_t)seed, (uint32_t)(seed >> 32)));

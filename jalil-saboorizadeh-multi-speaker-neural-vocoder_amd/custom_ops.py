@@ -403,11 +403,12 @@ def _(dstep):
 # ------------------------------------------------------------------ generation
 def _generate(weights, meta, cond, row_bias, noise, seed, row_offset, flags, return_logp,
               temperature=None, top_k=None, top_p=None, state=None, step0=0, prefix=None,
-              n_forced=None, return_state=False):
-    """The one path into the library's generation (srnn_generate5), behind the four registered
+              n_forced=None, return_state=False, noise_row=None, row_step0=None):
+    """The one path into the library's generation (srnn_generate6), behind the five registered
     ops, which check their arguments first: allocates seq (q_zero history, the prefix written
-    in), logp, the end state and the workspace, fills SrnnGenStream and calls.  Everything at
-    its default launches the plain kernels.  Returns (seq, logp, end state or empty)."""
+    in), logp, the end state and the workspace, fills SrnnGenStream and SrnnGenRows and calls.
+    Everything at its default launches the plain kernels.  Returns (seq, logp, end state or
+    empty)."""
     import ctypes
     import model
     m = model.srnn_model_struct(weights, meta)
@@ -435,10 +436,12 @@ def _generate(weights, meta, cond, row_bias, noise, seed, row_offset, flags, ret
     sz = ctypes.c_size_t(0)
     H.lib().call('srnn_gen_workspace_size', ctypes.byref(m), n_seqs, ctypes.byref(sz))
     ws = torch.empty(sz.value, device=dev, dtype=torch.uint8)
-    H.lib().call('srnn_generate5', ctypes.byref(m), n_seqs, num_cond, H.ptr(cond),
+    rows = H.SrnnGenRows(H.ptr(noise_row), H.ptr(row_step0))
+    H.lib().call('srnn_generate6', ctypes.byref(m), n_seqs, num_cond, H.ptr(cond),
                  H.ptr(row_bias), H.ptr(noise), int(seed) & ((1 << 64) - 1), int(row_offset),
                  H.ptr(seq), H.ptr(logp) if return_logp else None, H.ptr(ws), sz.value, int(flags),
-                 H.stream(), H.ptr(temperature), H.ptr(top_k), H.ptr(top_p), ctypes.byref(st))
+                 H.stream(), H.ptr(temperature), H.ptr(top_k), H.ptr(top_p), ctypes.byref(st),
+                 ctypes.byref(rows) if noise_row is not None or row_step0 is not None else None)
     return seq, logp, out_state
 
 
@@ -554,6 +557,15 @@ def generate_stream(weights: list[Tensor], meta: list[int], cond: Tensor, row_bi
                   None = P for every row
       return_state  also return the state the call ends in, else an empty tensor
     Returns (seq (n_seqs, L + T) int64, logp (T, n_seqs, Q) or empty, state)."""
+    return _generate_stream('generate_stream', weights, meta, cond, row_bias, noise, seed,
+                            row_offset, flags, return_logp, temperature, top_k, top_p, state, step0,
+                            prefix, prefix_len, return_state)
+
+
+def _generate_stream(op, weights, meta, cond, row_bias, noise, seed, row_offset, flags,
+                     return_logp, temperature, top_k, top_p, state, step0, prefix, prefix_len,
+                     return_state, noise_row=None, row_step0=None):
+    """The argument checks and the call of srnn::generate_stream and srnn::generate_rows."""
     n_seqs, dev = cond.shape[0], cond.device
     T = cond.shape[1] * meta[-1]            # steps of the call (meta: _generate_fake)
     ctl = [(n, t, dt) for n, t, dt in (('temperature', temperature, torch.float32),
@@ -561,17 +573,29 @@ def generate_stream(weights: list[Tensor], meta: list[int], cond: Tensor, row_bi
                                        ('top_p', top_p, torch.float32)) if t is not None]
     if prefix_len is not None:
         if prefix is None:
-            raise ValueError('generate_stream: prefix_len without a prefix')
+            raise ValueError(op + ': prefix_len without a prefix')
         ctl.append(('prefix_len', prefix_len, torch.int32))
-    _check_rows('generate_stream', n_seqs, dev, *ctl)
+    if noise_row is not None:
+        ctl.append(('noise_row', noise_row, torch.int32))
+    if row_step0 is not None:
+        # (uint32 counters travel as the int64 tensor the schema can carry)
+        ctl.append(('row_step0', row_step0, torch.int64))
+    _check_rows(op, n_seqs, dev, *ctl)
+    if noise_row is not None and int(noise_row.min()) < 0:
+        raise ValueError(op + ': noise_row must be >= 0')
+    if row_step0 is not None:
+        if int(row_step0.min()) < 0 or int(row_step0.max()) + T > 0xFFFFFFFF:
+            raise ValueError(op + ': row_step0 + %d steps do not fit the 32-bit counter' % T)
+        # the low words of the little-endian int64s: the library's uint32 array
+        row_step0 = row_step0.view(torch.int32)[::2].contiguous()
     if step0 < 0 or step0 + T > 0xFFFFFFFF:
-        raise ValueError('generate_stream: step0 %d + %d steps do not fit the 32-bit counter'
+        raise ValueError(op + ': step0 %d + %d steps do not fit the 32-bit counter'
                          % (step0, T))
     n_forced = None
     if prefix is not None:
         if (prefix.dim() != 2 or prefix.shape[0] != n_seqs or prefix.shape[1] > T or
                 prefix.dtype != torch.int64 or prefix.device != dev):
-            raise ValueError('generate_stream: prefix must be an (n_seqs, <= %d) int64 tensor '
+            raise ValueError(op + ': prefix must be an (n_seqs, <= %d) int64 tensor '
                              'on %s' % (T, dev))
         P = prefix.shape[1]
         n_forced = (prefix_len.clamp(0, P) if prefix_len is not None else
@@ -579,11 +603,12 @@ def generate_stream(weights: list[Tensor], meta: list[int], cond: Tensor, row_bi
     if state is not None:
         if (state.dtype != torch.uint8 or state.dim() != 2 or state.shape[0] != n_seqs or
                 state.device != dev):
-            raise ValueError('generate_stream: state must be an (n_seqs, row_bytes) uint8 tensor '
+            raise ValueError(op + ': state must be an (n_seqs, row_bytes) uint8 tensor '
                              'on %s' % dev)
         state = state.contiguous()
     return _generate(weights, meta, cond, row_bias, noise, seed, row_offset, flags, return_logp,
-                     temperature, top_k, top_p, state, step0, prefix, n_forced, return_state)
+                     temperature, top_k, top_p, state, step0, prefix, n_forced, return_state,
+                     noise_row, row_step0)
 
 
 @generate_stream.register_fake
@@ -592,6 +617,58 @@ def _(weights, meta, cond, row_bias, noise, seed, row_offset, flags, return_logp
     seq, logp = _generate_fake(meta, cond, return_logp)
     rows = (cond.shape[0], gen_state_row_bytes(meta)) if return_state else (0,)
     return seq, logp, cond.new_empty(rows, dtype=torch.uint8)
+
+
+@torch.library.custom_op('srnn::generate_rows', mutates_args=())
+def generate_rows(weights: list[Tensor], meta: list[int], cond: Tensor, row_bias: Tensor,
+                  noise: Optional[Tensor], seed: int, row_offset: int, flags: int,
+                  return_logp: bool, temperature: Optional[Tensor], top_k: Optional[Tensor],
+                  top_p: Optional[Tensor], state: Optional[Tensor], step0: int,
+                  prefix: Optional[Tensor], prefix_len: Optional[Tensor], return_state: bool,
+                  noise_row: Optional[Tensor],
+                  row_step0: Optional[Tensor]) -> tuple[Tensor, Tensor, Tensor]:
+    """srnn::generate_stream whose rows have their own Philox origins (srnn_generate6):
+      noise_row   (n_seqs,) int32 >= 0: the Philox row of local row b in place of
+                  row_offset + b (equal values draw equal noise), or None
+      row_step0   (n_seqs,) int64 in [0, 2^32 - T]: the Philox step of row b's first sample in
+                  place of step0, or None
+    Both only move Philox counters (a replayed `noise` and the log-probs keep their index from
+    the call's first step); both None: srnn::generate_stream's call."""
+    return _generate_stream('generate_rows', weights, meta, cond, row_bias, noise, seed,
+                            row_offset, flags, return_logp, temperature, top_k, top_p, state, step0,
+                            prefix, prefix_len, return_state, noise_row, row_step0)
+
+
+@generate_rows.register_fake
+def _(weights, meta, cond, row_bias, noise, seed, row_offset, flags, return_logp, temperature,
+      top_k, top_p, state, step0, prefix, prefix_len, return_state, noise_row, row_step0):
+    seq, logp = _generate_fake(meta, cond, return_logp)
+    rows = (cond.shape[0], gen_state_row_bytes(meta)) if return_state else (0,)
+    return seq, logp, cond.new_empty(rows, dtype=torch.uint8)
+
+
+@torch.library.custom_op('srnn::gen_state_fresh', mutates_args=())
+def gen_state_fresh(weights: list[Tensor], meta: list[int], n_seqs: int) -> Tensor:
+    """(n_seqs, row_bytes) uint8 records of rows that have done no step (srnn_gen_state_fresh):
+    a call of n_seqs rows from them is the call from no state, bit for bit."""
+    import ctypes
+    import model
+    if n_seqs < 1:
+        raise ValueError('gen_state_fresh: n_seqs must be >= 1')
+    m = model.srnn_model_struct(weights, meta)
+    dev = weights[0].device
+    out = torch.empty((n_seqs, gen_state_row_bytes(meta)), dtype=torch.uint8, device=dev)
+    sz = ctypes.c_size_t(0)
+    H.lib().call('srnn_gen_workspace_size', ctypes.byref(m), n_seqs, ctypes.byref(sz))
+    ws = torch.empty(sz.value, device=dev, dtype=torch.uint8)
+    H.lib().call('srnn_gen_state_fresh', ctypes.byref(m), n_seqs, H.ptr(out), out.numel(),
+                 H.ptr(ws), sz.value, H.stream())
+    return out
+
+
+@gen_state_fresh.register_fake
+def _(weights, meta, n_seqs):
+    return weights[0].new_empty((n_seqs, gen_state_row_bytes(meta)), dtype=torch.uint8)
 
 
 @torch.library.custom_op('srnn::sample_rows', mutates_args=())
@@ -638,4 +715,4 @@ def _(logits, noise, seed, row0, step, temperature, top_k, top_p, return_logp):
 
 OPS = ('tier_fwd', 'tier_bwd', 'mlp_fwd', 'mlp_bwd', 'nll_bits', 'nll_bits_bwd', 'upsample',
        'upsample_bwd', 'dequant', 'adam_clip_', 'step_advance_', 'generate', 'generate_ctrl',
-       'generate_ctrl_p', 'generate_stream', 'sample_rows')
+       'generate_ctrl_p', 'generate_stream', 'generate_rows', 'gen_state_fresh', 'sample_rows')

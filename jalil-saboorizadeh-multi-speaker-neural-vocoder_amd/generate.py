@@ -74,6 +74,7 @@ default_params = {
     'top_k': 0,
     'top_p': 1.0,
     'chunk_frames': 0,
+    'slots': 0,
 }
 
 
@@ -186,6 +187,14 @@ def main(frame_sizes, **params):
         if original == '..':
             original = name.split('/')[3]
         jobs.append((cond_dir + name, speaker, original))
+    if params['slots'] > 0:
+        # continuous batching (Generator.serve): the files through a fixed number of rows
+        if not params['batch_files']:
+            sys.exit('--slots needs --batch_files True.')
+        if params['sampler'] != 'philox':
+            sys.exit('--slots serves with the device sampler only: pass --sampler philox.')
+        if world > 1:
+            sys.exit('--slots runs in a single process.')
     if params['batch_files']:
         init_random_seed(params['seed'], use_cuda)
         model = build_model(params, spk_dim, use_cuda)
@@ -201,7 +210,16 @@ def main(frame_sizes, **params):
         gen = Generator(model, use_cuda)
         ctrl = dict(temperature=params['temperature'], top_k=params['top_k'],
                     top_p=params['top_p'])
-        if world > 1:
+        if params['slots'] > 0:
+            # stream ids j n + i: the Philox rows of the padded batch below
+            given = {k: v for k, v in ctrl.items() if v != default_params[k]}
+            reqs = [dict(cond=conds[j], spk=jobs[j][1], stream_id=j * n + i, **given)
+                    for j in range(len(jobs)) for i in range(n)]
+            out = np.zeros((len(rows), n_cond * model.lookback), dtype=np.float32)
+            for u, samples in gen.serve(reqs, params['slots'], params['chunk_frames'] or 32,
+                                        seed=params['seed']):
+                out[u, :samples.shape[0]] = samples.numpy()
+        elif world > 1:
             # rank-sharded: contiguous row shards gathered at the end (rows
             # padded to a multiple of the world size); either sampler reproduces the
             # single-process stream (shard_generate)
@@ -265,7 +283,7 @@ def build_parser():
                       ('cond_list', str), ('spk_list', str), ('sampler', str),
                       ('batch_files', parse_bool), ('compute_dtype', str),
                       ('temperature', float), ('top_k', int), ('top_p', float),
-                      ('chunk_frames', int)):
+                      ('chunk_frames', int), ('slots', int)):
         p.add_argument('--' + name, type=typ)
     # gen.sh passes --results_path (generate.py has no such option; accepted and ignored)
     p.add_argument('--results_path', type=str)

@@ -1072,6 +1072,76 @@ def nucleus_control(n_seqs, top_p=1.0):
     return torch.from_numpy(p32.copy())
 
 
+def stream_rows(n_seqs, stream_ids):
+    """Generator.__call__'s stream_ids as a host tensor (a pure host function, beside
+    sampling_controls): None, or an integer sequence, array or tensor of length n_seqs with every
+    value in [0, 2^31) -- the Philox row of each local row (duplicates allowed: such rows draw the
+    same noise).  Returns None or an (n_seqs,) int32 tensor.  Raises ValueError otherwise."""
+    if stream_ids is None:
+        return None
+    a = (stream_ids.detach().cpu().numpy() if torch.is_tensor(stream_ids)
+         else np.asarray(stream_ids))
+    if a.dtype == object or a.dtype.kind not in 'iuf':
+        raise ValueError('stream_rows: stream_ids must be integers')
+    if a.ndim != 1 or a.shape[0] != n_seqs:
+        raise ValueError('stream_rows: stream_ids has shape %s, expected (%d,)'
+                         % (tuple(a.shape), n_seqs))
+    if a.dtype.kind == 'f':
+        if not np.all(np.isfinite(a)) or np.any(a != np.round(a)):
+            raise ValueError('stream_rows: stream_ids must be integral')
+        a = a.astype(np.float64)
+    if np.any(a < 0) or np.any(a >= 2 ** 31):
+        raise ValueError('stream_rows: stream_ids must lie in [0, 2^31)')
+    return torch.from_numpy(a.astype(np.int32))
+
+
+def serve_plan(lengths, slots, chunk_frames):
+    """The calls by which Generator.serve runs requests of `lengths` conditioning frames through
+    `slots` rows, at most chunk_frames frames per call (a pure host function).  Returns a list of
+    (n, rows): n the call's frame count and rows, per slot, (request or None, f0, f1, fresh) --
+    the slot generates frames [f0, f1) of the request, from a fresh record when `fresh`.
+    The policy:
+      * slot s starts with request s;
+      * a call runs n = min(chunk_frames, largest remainder over the active slots) frames; an
+        active slot produces min(n, remainder) of them (its row still runs n, on zero-padded
+        conditioning: the surplus is trimmed and the row's state dropped);
+      * after the call finished requests complete in slot order, then the free slots take the
+        pending requests in request order, lowest slot first, each from a fresh record;
+      * a slot with nothing to do carries a dummy row (None, 0, 0, True);
+      * the plan ends when no slot is active."""
+    lengths = [int(v) for v in lengths]
+    slots, chunk_frames = int(slots), int(chunk_frames)
+    if slots < 1 or chunk_frames < 1:
+        raise ValueError('serve_plan: slots and chunk_frames must be >= 1')
+    if any(v < 1 for v in lengths):
+        raise ValueError('serve_plan: every request needs at least one frame')
+    nxt = min(slots, len(lengths))
+    req = [s if s < nxt else None for s in range(slots)]
+    done = [0] * slots
+    fresh = [True] * slots
+    plan = []
+    while any(r is not None for r in req):
+        n = min(chunk_frames, max(lengths[r] - done[s] for s, r in enumerate(req)
+                                  if r is not None))
+        rows = []
+        for s, r in enumerate(req):
+            if r is None:
+                rows.append((None, 0, 0, True))
+                continue
+            f1 = min(lengths[r], done[s] + n)
+            rows.append((r, done[s], f1, fresh[s]))
+            done[s], fresh[s] = f1, False
+        plan.append((n, rows))
+        for s, r in enumerate(req):
+            if r is not None and done[s] == lengths[r]:
+                req[s] = None
+        for s in range(slots):
+            if req[s] is None and nxt < len(lengths):
+                req[s], done[s], fresh[s] = nxt, 0, True
+                nxt += 1
+    return plan
+
+
 def gen_state_layout(meta):
     """[dtype, n_tiers, n_rnn, dim, lookback, row_bytes] of a GenState for generation_weights'
     meta under the process's fold switches."""
@@ -1112,6 +1182,37 @@ class GenState:
             raise IndexError('GenState.rows: row numbers must lie in [0, %d)' % self.n_seqs)
         return GenState(self.blob[idx.to(self.blob.device)].contiguous(), self.layout,
                         self.steps[idx].clone())
+
+    @classmethod
+    def cat(cls, states):
+        """The rows of `states` (GenStates of one layout, on one device), one after another."""
+        states = list(states)
+        if not states or not all(isinstance(st, GenState) for st in states):
+            raise ValueError('GenState.cat: a non-empty sequence of GenStates')
+        for st in states[1:]:
+            if st.layout != states[0].layout:
+                raise ValueError('GenState.cat: layouts differ: %s and %s'
+                                 % (states[0].layout, st.layout))
+        return cls(torch.cat([st.blob for st in states]), states[0].layout,
+                   torch.cat([st.steps for st in states]))
+
+    def replace(self, index, other):
+        """A new state whose rows `index` (distinct row numbers) are `other`'s rows, in order,
+        step counts included; the rest are this state's."""
+        idx = torch.as_tensor(index, dtype=torch.long).reshape(-1).cpu()
+        if not isinstance(other, GenState) or other.layout != self.layout:
+            raise ValueError('GenState.replace: the other state has another layout')
+        if idx.numel() != other.n_seqs:
+            raise ValueError('GenState.replace: %d row numbers for %d rows'
+                             % (idx.numel(), other.n_seqs))
+        if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= self.n_seqs):
+            raise IndexError('GenState.replace: row numbers must lie in [0, %d)' % self.n_seqs)
+        if idx.unique().numel() != idx.numel():
+            raise ValueError('GenState.replace: row numbers must be distinct')
+        blob, steps = self.blob.clone(), self.steps.clone()
+        blob[idx.to(blob.device)] = other.blob.to(blob.device)
+        steps[idx] = other.steps
+        return GenState(blob, self.layout, steps)
 
     def to(self, device):
         return GenState(self.blob.to(device), self.layout, self.steps)
@@ -1212,6 +1313,15 @@ class Generator(Runner):
     log-probs are still reported and noise still consumed at those steps, and a forced step
     overrides temperature, top_k and top_p.  stream() yields an utterance chunk by chunk,
     prime() returns the state after given audio.
+
+    Continuous batching (not in the reference).  stream_ids (stream_rows: one integer in
+    [0, 2^31) per row) names the Philox row of each local row in place of row_offset + b, and
+    under sampler='philox' every row then draws from its own state.steps[b] on, so the rows of
+    `state` may be at differing step counts: a stream keeps its noise whichever row serves it
+    and whatever its neighbours are doing.  With replayed noise stream_ids has no effect.
+    fresh_state() returns records of rows that have done no step (a call from them is the call
+    from state=None), GenState.cat / replace join states, and serve() runs requests of differing
+    lengths through a fixed number of rows (serve_plan states the policy).
     """
 
     def __init__(self, model, cuda=False):
@@ -1219,11 +1329,12 @@ class Generator(Runner):
         self.cuda = cuda
         self.last_sequences = None
         self.last_state = None
+        self.last_serve = None
 
     def __call__(self, n_seqs, seq_len, cond, spk, sampler='torch', seed=0, noise=None,
                  return_logp=False, use_graph=True, dtype=None, persistent=True, row_offset=0,
                  temperature=1.0, top_k=0, top_p=1.0, state=None, return_state=False,
-                 prefix=None, prefix_len=None):
+                 prefix=None, prefix_len=None, stream_ids=None, controls_level=0):
         """row_offset: these n_seqs rows are rows [row_offset, row_offset + n_seqs) of a larger
         batch (rank-sharded generation, see shard_generate): the Philox noise (sampler='philox')
         is that of the global rows, so shards reproduce the single-process stream.
@@ -1232,7 +1343,10 @@ class Generator(Runner):
         without top_p.  return_logp's log-probs are the model's
         log-softmax whatever the controls.
         state, return_state, prefix, prefix_len: streaming (class docstring); at their defaults
-        the call launches exactly what it launches without them."""
+        the call launches exactly what it launches without them.
+        stream_ids: the rows' Philox rows and, with `state`, their own step origins (class
+        docstring); None: nothing changes.  controls_level: 1 / 2 passes the control arrays of
+        that level even where every row is at its defaults (serve: one build for all calls)."""
         model = self.model
         self.reset_hidden_states()
         dev = next(model.parameters()).device
@@ -1251,7 +1365,10 @@ class Generator(Runner):
         Q = model.q_levels
         ctrl = sampling_controls(n_seqs, temperature, top_k, Q)
         nucleus = nucleus_control(n_seqs, top_p)
-        if nucleus is not None and ctrl is None:
+        ids = stream_rows(n_seqs, stream_ids)
+        if controls_level >= 2 and nucleus is None:
+            nucleus = torch.ones(n_seqs, dtype=torch.float32)
+        if (nucleus is not None or controls_level >= 1) and ctrl is None:
             ctrl = (torch.ones(n_seqs, dtype=torch.float32), torch.zeros(n_seqs, dtype=torch.int32))
         weights, meta = generation_weights(model, dtype)
         row_bias = top_row_bias(model, spk)
@@ -1262,11 +1379,13 @@ class Generator(Runner):
             assert noise.shape == (T, n_seqs, Q), 'noise must be (T, n_seqs, Q)'
         # the registered op srnn::generate (custom_ops.py): the whole sample loop on the device
         # (with sampling controls: srnn::generate_ctrl, the same loop with them in the draw)
+        philox = noise is None
+        if not philox:
+            ids = None                   # (replayed noise: indexed by the call's own rows)
         streaming = (state is not None or return_state or prefix is not None or
-                     prefix_len is not None)
+                     prefix_len is not None or ids is not None)
         if streaming:
-            philox = noise is None
-            state_blob, step0 = self._stream_state(state, n_seqs, dev, philox)
+            state_blob, step0 = self._stream_state(state, n_seqs, dev, philox and ids is None)
             prefix, prefix_len = forced_prefix(model, n_seqs, T, prefix, prefix_len)
         with torch.no_grad():
             args = (weights, meta, cond, row_bias, noise, int(seed) & ((1 << 63) - 1),
@@ -1275,12 +1394,18 @@ class Generator(Runner):
             if streaming:
                 # srnn::generate_stream: the same loop from a carried state and / or along a
                 # forced prefix (srnn_generate5); controls at their defaults stay None
-                seq, logp, blob = torch.ops.srnn.generate_stream(
-                    *args, ctrl[0].to(dev) if ctrl is not None else None,
+                sargs = args + (
+                    ctrl[0].to(dev) if ctrl is not None else None,
                     ctrl[1].to(dev) if ctrl is not None else None,
                     nucleus.to(dev) if nucleus is not None else None, state_blob, step0,
                     prefix.to(dev) if prefix is not None else None,
                     prefix_len.to(dev) if prefix_len is not None else None, bool(return_state))
+                if ids is None:
+                    seq, logp, blob = torch.ops.srnn.generate_stream(*sargs)
+                else:
+                    # srnn::generate_rows: with the rows' own Philox origins (srnn_generate6)
+                    seq, logp, blob = torch.ops.srnn.generate_rows(
+                        *sargs, ids.to(dev), state.steps.to(dev) if state is not None else None)
             elif ctrl is None:
                 seq, logp = torch.ops.srnn.generate(*args)
             elif nucleus is not None:
@@ -1310,7 +1435,7 @@ class Generator(Runner):
             raise ValueError('Generator: state holds %d rows, the call has %d'
                              % (state.n_seqs, n_seqs))
         step0 = 0
-        if philox:
+        if philox:      # (and no stream_ids: with them every row has its own origin)
             # one step origin per call: the device noise of step t is Philox(row, step0 + t)
             if bool((state.steps != state.steps[0]).any()):
                 raise ValueError('Generator: rows at differing step counts %s cannot continue '
@@ -1318,6 +1443,81 @@ class Generator(Runner):
                                  % sorted(set(state.steps.tolist())))
             step0 = int(state.steps[0])
         return state.blob.to(dev), step0
+
+    def fresh_state(self, n_seqs, dtype=None):
+        """The GenState of n_seqs rows that have done no step (srnn::gen_state_fresh): h0, the
+        q_zero history and, with folded ticks, their carried products as a fresh start of n_seqs
+        rows computes them.  A call with state=fresh_state(n_seqs) equals the call with
+        state=None bit for bit, and every row of the result is the same record."""
+        n_seqs = int(n_seqs)
+        dev = next(self.model.parameters()).device
+        H.need_cuda(torch.empty(0, device=dev))
+        weights, meta = generation_weights(self.model, dtype)
+        with torch.no_grad():
+            blob = torch.ops.srnn.gen_state_fresh(weights, meta, n_seqs)
+        return GenState(blob, gen_state_layout(meta), torch.zeros(n_seqs, dtype=torch.int64))
+
+    def serve(self, requests, slots, chunk_frames, seed=0, dtype=None, persistent=True,
+              use_graph=True):
+        """Continuous batching: runs `requests` -- dicts with cond (F_u, C) and spk, optionally
+        stream_id (default: the request's position), temperature, top_k, top_p -- through `slots`
+        rows by serve_plan's calls (sampler='philox' only), and yields (position, host float32
+        (F_u * lookback,) samples) as requests complete.  Request u's samples are row 0 of the
+        one-shot self(slots, 0, cond_u, spk_u, sampler='philox', seed=seed,
+        row_offset=stream_id_u, <u's controls>), sample for sample.  If any request carries a
+        control, every call passes per-row control arrays (defaults for the other rows).
+        self.last_serve: {'calls', 'frames' (per call), 'row_frames'} of the run."""
+        requests = list(requests)
+        slots = int(slots)
+        conds = []
+        for u, rq in enumerate(requests):
+            c = rq['cond']
+            c = torch.as_tensor(np.asarray(c) if not torch.is_tensor(c) else c)
+            if c.dim() != 2 or c.shape[0] < 1:
+                raise ValueError('Generator.serve: request %d: cond must be (frames >= 1, C)' % u)
+            conds.append(c.to(torch.float32).cpu())
+        plan = serve_plan([c.shape[0] for c in conds], slots, chunk_frames)
+        ids = [int(rq.get('stream_id', u)) for u, rq in enumerate(requests)]
+        level = (2 if any('top_p' in rq for rq in requests) else
+                 1 if any('temperature' in rq or 'top_k' in rq for rq in requests) else 0)
+        L = self.model.lookback
+        self.last_serve = {'calls': 0, 'frames': [], 'row_frames': 0}
+        if not plan:
+            return
+        C = conds[0].shape[1]
+        fresh = self.fresh_state(slots, dtype)
+        state = fresh
+        parts = {}
+        for n, rows in plan:
+            cond = torch.zeros(slots, n, C)
+            spk = torch.zeros(slots, dtype=torch.long)
+            sid = torch.zeros(slots, dtype=torch.int64)
+            tau, k, p = [1.0] * slots, [0] * slots, [1.0] * slots
+            for s, (u, f0, f1, _) in enumerate(rows):
+                if u is None:
+                    continue
+                rq = requests[u]
+                cond[s, :f1 - f0] = conds[u][f0:f1]
+                spk[s] = int(torch.as_tensor(rq['spk']).reshape(-1)[0])
+                sid[s] = ids[u]
+                tau[s], k[s], p[s] = (rq.get('temperature', 1.0), rq.get('top_k', 0),
+                                      rq.get('top_p', 1.0))
+            new = [s for s, row in enumerate(rows) if row[3]]
+            if new:
+                state = state.replace(new, fresh.rows(new))
+            out, state = self(slots, 0, cond, spk, sampler='philox', seed=seed, dtype=dtype,
+                              persistent=persistent, use_graph=use_graph, state=state,
+                              return_state=True, stream_ids=sid, temperature=tau, top_k=k,
+                              top_p=p, controls_level=level)
+            self.last_serve['calls'] += 1
+            self.last_serve['frames'].append(n)
+            self.last_serve['row_frames'] += slots * n
+            for s, (u, f0, f1, _) in enumerate(rows):
+                if u is None:
+                    continue
+                parts.setdefault(u, []).append(out[s, :(f1 - f0) * L])
+                if f1 == conds[u].shape[0]:
+                    yield u, torch.cat(parts.pop(u))
 
     def stream(self, n_seqs, cond, spk, chunk_frames, state=None, **kw):
         """Generates chunk_frames conditioning frames per call of __call__, each continuing from

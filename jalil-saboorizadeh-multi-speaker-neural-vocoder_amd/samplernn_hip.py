@@ -96,6 +96,9 @@ _SIGS = {
     'srnn_generate4': [_P, _I, _I, _P, _P, _P, _U64, _I, _P, _P, _P, _SZ, _I, _P, _P, _P, _P],
     'srnn_generate5': [_P, _I, _I, _P, _P, _P, _U64, _I, _P, _P, _P, _SZ, _I, _P, _P, _P, _P,
                        _P],
+    'srnn_generate6': [_P, _I, _I, _P, _P, _P, _U64, _I, _P, _P, _P, _SZ, _I, _P, _P, _P, _P,
+                       _P, _P],
+    'srnn_gen_state_fresh': [_P, _I, _P, _SZ, _P, _SZ, _P],
     'srnn_gen_state_bytes': [_P, _I],          # (returns size_t, not a status: see _Lib)
     'srnn_sample_rows': [_P, _L, _I, _P, _U64, _I, _I, _P, _P, _P, _P, _P, _P],
     'srnn_persistent_flag_to_f32': [_P, _P],
@@ -133,6 +136,12 @@ class SrnnGenStream(ctypes.Structure):
     None), their size, the Philox step origin and the rows' forced prefix lengths."""
     _fields_ = [('state_in', _P), ('state_out', _P), ('state_bytes', _SZ),
                 ('step0', ctypes.c_uint32), ('n_forced', _P)]
+
+
+class SrnnGenRows(ctypes.Structure):
+    """The C ABI's SrnnGenRows (srnn_generate6): the rows' own Philox rows and step origins
+    (device pointers or None)."""
+    _fields_ = [('noise_row', _P), ('step0', _P)]
 
 
 EPI_AMAX, EPI_BLK, EPI_CSUM, EPI_LOGSOFTMAX = 1, 2, 4, 8
