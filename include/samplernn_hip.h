@@ -123,8 +123,38 @@ int srnn_gemm_bits(int dtype, int out_dtype, int transA, int transB, int M, int 
 int srnn_relu_bits(int dtype, const void* a, int64_t lda, int M, int N, unsigned short* bits,
                    int64_t ldb, void* stream);
 
-/* ---- GRU (torch.nn.GRU, model.py:148-165,244) -----------------------------------------
- * One time step for B rows: h_t from h_{t-1} and either x (gi computed in-kernel with
+/* ---- GRU (torch.nn.GRU, model.py:148-165,244): one layer over a whole sequence ----------
+ * (csrc/gru_layer.hpp).
+ * The library picks the back end for (dtype, B, D) on this device: the XCD-grouped
+ * persistent sweep, the LDS-resident persistent sweep, or one srnn_gru_cell launch per step
+ * (fp32 always; SRNN_GRU_XCD=0 / SRNN_GRU_SEQ=0 switch a sweep off).  srnn_gru_layer_plan
+ * names it and gives the work bytes of either direction (0: pass no work buffer);
+ * _plan_for is the same for a device of `ncu` CUs shared by `share` processes. */
+enum SrnnGruBackend { SRNN_GRU_STEPS = 0, SRNN_GRU_SEQ = 1, SRNN_GRU_XCD = 2 };
+int srnn_gru_layer_plan(int dtype, int B, int D, int* backend, size_t* fwd_bytes,
+                        size_t* bwd_bytes);
+int srnn_gru_layer_plan_for(int dtype, int B, int D, int ncu, int share, int* backend,
+                            size_t* fwd_bytes, size_t* bwd_bytes);
+/* Forward: x[b][t] = x + b*ld + t*s for gi (3D, includes b_ih), out / out_lp (D; out_lp in
+ * `dtype`, NULL in fp32) and gates (4D: r|z|n|gh_n); h0 (B, D) fp32.  hprev_lp (out_lp's
+ * layout): [h0, out[:, :Fr-1]] in bf16 for the W_hh gradient -- only the XCD back end
+ * writes it, pass NULL under any other plan. */
+int srnn_gru_layer_fwd(int dtype, int B, int D, int Fr, const float* gi, int64_t ldgi, int64_t sgi,
+                       const float* h0, const void* whh, const float* bhh, float* out,
+                       void* out_lp, int64_t ldo, int64_t so, float* gates, int64_t ldg,
+                       int64_t sg, void* hprev_lp, void* work, size_t work_bytes, void* stream);
+/* Backward (t = Fr-1 .. 0) from dy, the forward's gates / out (hout) / h0, W_hh (3D, D) and
+ * its transpose (D, 3D).  dgh / dgh_lp / dgi / dgi_lp share ldd / sd (3D per row and step);
+ * ddir0 (B, D) receives dh_direct of step 0.  XCD plan: dgh_lp required, dgh / dgi (fp32),
+ * dgi_lp and bsum ((B, 4D): sums over t of [dar | daz | dghn | dan]) optional.  Other plans:
+ * dgh, dgi (and dgh_lp in bf16) required, dgi_lp and bsum NULL. */
+int srnn_gru_layer_bwd(int dtype, int B, int D, int Fr, const float* dy, int64_t lddy, int64_t sdy,
+                       const float* gates, int64_t ldg, int64_t sg, const float* hout, int64_t ldo,
+                       int64_t so, const float* h0, const void* whh, const void* whh_t, float* dgh,
+                       void* dgh_lp, float* dgi, void* dgi_lp, float* bsum, int64_t ldd,
+                       int64_t sd, float* ddir0, void* work, size_t work_bytes, void* stream);
+
+/* One time step for B rows: h_t from h_{t-1} and either x (gi computed in-kernel with
  * W_ih) or a precomputed gi = x W_ih^T + b_ih.  Optionally saves r|z|n|gh_n (4D/row).  */
 int srnn_gru_cell(int dtype, int B, int D, int Din, const void* x, int64_t ldx, const void* wih,
                   const float* bih, const float* gi, int64_t ldgi, const void* h, int64_t ldh,
@@ -141,12 +171,28 @@ int srnn_gru_cell_bwd(int dtype, int B, int D, const float* dy, int64_t lddy,
                       const float* hprev, int64_t ldhp, float* dgh, int64_t lddgh, void* dgh_lp,
                       int64_t lddghl, float* dgi, int64_t lddgi, float* ddir, void* stream);
 
+/* ---- Forced forms: one back end whatever the plan says, for tests, the benchmark's isolated
+ * sweep and probes.  A call its back end does not take is an error ("not supported"); the
+ * three queries answer for their back end alone, and 0 while its switch is off. */
 /* Whole-sequence forward of one GRU layer in a single persistent launch (bf16, D <= 1024,
  * D % 128 == 0, (D/16) * ceil(B/32) workgroups co-resident): out[b][t] / out_lp /
  * gates[b][t] exactly as Fr calls of srnn_gru_cell with gi[b][t] = gi + b*ldgi + t*sgi.
  * work: >= (64 * ceil(B/32) + 1) ints (zeroed by the call; the last word is an error flag
  * raised if a workgroup gave up waiting).  srnn_gru_seq_supported returns 1 / 0.       */
 int srnn_gru_seq_supported(int dtype, int B, int D);
+int srnn_gru_seq_fwd(int dtype, int B, int D, int Fr, const float* gi, int64_t ldgi,
+                     int64_t sgi, const float* h0, const void* h0_lp, const void* whh,
+                     const float* bhh, float* out, void* out_lp, int64_t ldo, int64_t so,
+                     float* gates, int64_t ldg, int64_t sg, int* work, size_t work_bytes,
+                     void* stream);
+/* Whole-sequence backward of one GRU layer (t = Fr-1 .. 0) in one persistent launch:
+ * the Fr calls of srnn_gru_cell_bwd, with dh_direct kept on chip; ddir0 receives the
+ * dh_direct of step 0.  dgh / dgh_lp / dgi share the row stride ldd and step stride sd.  */
+int srnn_gru_seq_bwd(int dtype, int B, int D, int Fr, const float* dy, int64_t lddy,
+                     int64_t sdy, const float* gates, int64_t ldg, int64_t sg, const float* hout,
+                     int64_t ldo, int64_t so, const float* h0, const void* whh_t, float* dgh,
+                     void* dgh_lp, float* dgi, int64_t ldd, int64_t sd, float* ddir0, int* work,
+                     size_t work_bytes, void* stream);
 /* Whole-sequence GRU forward of one layer as ONE persistent launch with row groups placed per
  * XCD (gru_xcd.hip): W_hh resident in VGPRs, h hand-offs as data-tagged granules in the XCD's
  * L2.  Any B: up to 4 tiles of 16 rows per group (512 rows per launch at D = 1024; more rows run
@@ -214,19 +260,6 @@ int srnn_persistent_flag_snapshot(int* dst, void* stream);
 /* dtype (fp32 / bf16) forms of srnn_persistent_flag_to_f32 / _or_f32 (bf16 gradient buckets) */
 int srnn_persistent_flag_to(void* dst, int dtype, void* stream);
 int srnn_persistent_flag_or(const void* src, int dtype, void* stream);
-int srnn_gru_seq_fwd(int dtype, int B, int D, int Fr, const float* gi, int64_t ldgi,
-                     int64_t sgi, const float* h0, const void* h0_lp, const void* whh,
-                     const float* bhh, float* out, void* out_lp, int64_t ldo, int64_t so,
-                     float* gates, int64_t ldg, int64_t sg, int* work, size_t work_bytes,
-                     void* stream);
-/* Whole-sequence backward of one GRU layer (t = Fr-1 .. 0) in one persistent launch:
- * the Fr calls of srnn_gru_cell_bwd, with dh_direct kept on chip; ddir0 receives the
- * dh_direct of step 0.  dgh / dgh_lp / dgi share the row stride ldd and step stride sd.  */
-int srnn_gru_seq_bwd(int dtype, int B, int D, int Fr, const float* dy, int64_t lddy,
-                     int64_t sdy, const float* gates, int64_t ldg, int64_t sg, const float* hout,
-                     int64_t ldo, int64_t so, const float* h0, const void* whh_t, float* dgh,
-                     void* dgh_lp, float* dgi, int64_t ldd, int64_t sd, float* ddir0, int* work,
-                     size_t work_bytes, void* stream);
 
 /* ---- SampleLevelMLP (model.py:308-325) ----------------------------------------------
  * a1[b*Tlen+t] = relu(sum_k tab[k][x[b*ldx + xoff + t + k]] + upper[b*Tlen+t])

@@ -16,6 +16,7 @@
 #include "ulaw_tables.h"
 #include "../../include/samplernn_hip.h"
 #include "gen_mlp.hpp"
+#include "gru_layer.hpp"
 #include "sampler.hpp"
 
 int srnn_mlp_l1_impl(int dtype, const void* tab, const int64_t* x, int64_t ldx, int xoff,
@@ -32,15 +33,6 @@ int srnn_sample_origin_impl(const float* z, int64_t ldz, int B, const float* noi
                             const float* temperature, const int* top_k, const float* top_p,
                             uint32_t step0, const int* n_forced, const int* noise_row,
                             const uint32_t* row_step0, hipStream_t s);
-int srnn_gru_cell_impl(int dtype, int B, int D, int Din, const void* x, int64_t ldx,
-                       const void* wih, const float* bih, const float* gi, int64_t ldgi,
-                       const void* h, int64_t ldh, const float* hf, int64_t ldhf, const void* whh,
-                       const float* bhh, float* hout, int64_t ldho, void* hout_lp, int64_t ldhl,
-                       float* gates, int64_t ldgt, hipStream_t s);
-int srnn_gru_cell_x_impl(int dtype, int B, int D, int Din, const void* x, int64_t ldx,
-                         const void* wih, const float* bih, const float* gadd, int64_t ldgadd,
-                         const float* gh, int64_t ldgh, const float* hf, int64_t ldhf, float* hout,
-                         int64_t ldho, void* hout_lp, int64_t ldhl, hipStream_t s);
 
 // Fused tier input (build_input + input projection of one tier tick), one row per block:
 //   a[s] = 2*deq(seq[b, i - nfs + s]) (s < nfs) | cond[b, i/L - 1, s - nfs]   (rounded to T,

@@ -12,6 +12,7 @@
 #include "gemm_core.hpp"
 #include "ring_core.hpp"
 #include "gru_point.hpp"
+#include "gru_layer.hpp"
 #include "samplernn_hip_internal.hpp"
 
 // ring depth of the per-step GRU kernels: 8 slots (7 k-stages in flight) fit the 160 KiB
@@ -182,21 +183,14 @@ __global__ __launch_bounds__(256) void gru_cell_ring_kernel(GruCellArgs a) {
 template <typename T, int BM>
 static int launch_cell(GruCellArgs& a, hipStream_t s) {
     typedef Ring<T, 32, 48, 2, 1, 2, GRU_NS> R;
-    const int es = (int)sizeof(T);
     const bool ring = a.D % R::KB == 0 && (!a.x || a.Din % R::KB == 0) && a.vec_h && a.vec_whh &&
                       (!a.x || (a.vec_x && a.vec_wih));
     SRNN_REQUIRE(ring || (!a.ghp && !a.gadd), "gru_cell: precomputed gh / gadd need the ring shape");
     if (ring) {
-        static bool attr = false;
-        if (!attr) {
-            SRNN_CHECK_HIP(hipFuncSetAttribute((const void*)gru_cell_ring_kernel<T>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, R::LDS));
-            attr = true;
-        }
+        if (const int rc = srnn_raise_lds((const void*)gru_cell_ring_kernel<T>, R::LDS)) return rc;
         dim3 grid(cdiv(a.D, 16), cdiv(a.B, 32));
         hipLaunchKernelGGL((gru_cell_ring_kernel<T>), grid, dim3(256), R::LDS, s, a);
         SRNN_LAUNCH_CHECK();
-        (void)es;
         return 0;
     }
     constexpr int WM = BM / 16, WK = 4 / WM;
@@ -358,12 +352,7 @@ template <typename T, int BM>
 static int launch_bwd(GruBwdArgs& a, hipStream_t s) {
     typedef Ring<T, 32, 16, 2, 1, 2, GRU_NS> R;
     if (a.whh_t && (3 * a.D) % R::KB == 0 && a.vec_wt && (!a.dgh_next || a.vec_dgn)) {
-        static bool attr = false;
-        if (!attr) {
-            SRNN_CHECK_HIP(hipFuncSetAttribute((const void*)gru_bwd_ring_kernel<T>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, R::LDS));
-            attr = true;
-        }
+        if (const int rc = srnn_raise_lds((const void*)gru_bwd_ring_kernel<T>, R::LDS)) return rc;
         dim3 grid(cdiv(a.D, 16), cdiv(a.B, 32));
         hipLaunchKernelGGL((gru_bwd_ring_kernel<T>), grid, dim3(256), R::LDS, s, a);
         SRNN_LAUNCH_CHECK();

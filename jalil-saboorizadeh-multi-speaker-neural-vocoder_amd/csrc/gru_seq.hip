@@ -14,6 +14,7 @@
 // per-step ring kernel's, so both paths give identical bits.
 #include "ring_core.hpp"
 #include "gru_point.hpp"
+#include "gru_layer.hpp"
 #include "samplernn_hip_internal.hpp"
 
 namespace gseq {
@@ -364,96 +365,65 @@ __global__ __launch_bounds__(256, 1) void gru_seq_bwd_kernel(GruSeqBwdArgs a) {
     }
 }
 
-
-// 1 if the persistent path can run this shape on this device, else 0
-extern "C" int srnn_gru_seq_supported(int dtype, int B, int D) {
-    if (dtype != SRNN_BF16 || D % 128 != 0 || D > gseq::MAXK || B <= 0) return 0;
-    // every workgroup must be co-resident (one per CU: 160 KiB LDS each, for every process
-    // sharing the device, persist.hip); <= 64 unit tiles
-    return D / 16 <= 64 && srnn_persist_fits_cus((int64_t)(D / 16) * cdiv(B, gseq::BM)) ? 1 : 0;
-}
-
-extern "C" int srnn_gru_seq_bwd(int dtype, int B, int D, int Fr, const float* dy, int64_t lddy,
-                                int64_t sdy, const float* gates, int64_t ldg, int64_t sg,
-                                const float* hout, int64_t ldo, int64_t so, const float* h0,
-                                const void* whh_t, float* dgh, void* dgh_lp, float* dgi,
-                                int64_t ldd, int64_t sd, float* ddir0, int* work,
-                                size_t work_bytes, void* stream) {
-    SRNN_REQUIRE(srnn_gru_seq_supported(dtype, B, D), "gru_seq: shape/device not supported");
-    SRNN_REQUIRE(3 * D <= gseqb::MAXK && (3 * D) % gseqb::R::KB == 0, "gru_seq_bwd: D");
-    const int nm = cdiv(B, gseqb::BM);
-    const size_t words = (size_t)nm * 64 + 1;
-    SRNN_REQUIRE(work && work_bytes >= words * sizeof(int), "gru_seq_bwd: workspace");
-    if (Fr <= 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    SRNN_CHECK_HIP(hipMemsetAsync(work, 0, words * sizeof(int), s));
-    static bool attr = false;
-    if (!attr) {
-        SRNN_CHECK_HIP(hipFuncSetAttribute((const void*)gru_seq_bwd_kernel,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           gseqb::LDS));
-        attr = true;
-    }
-    GruSeqBwdArgs a;
-    a.dy = dy; a.lddy = lddy; a.sdy = sdy;
-    a.gates = gates; a.ldg = ldg; a.sg = sg;
-    a.hout = hout; a.ldo = ldo; a.so = so; a.h0 = h0;
-    a.whh_t = (const bf16*)whh_t;
-    a.dgh = dgh; a.dgh_lp = (bf16*)dgh_lp; a.dgi = dgi; a.ldd = ldd; a.sd = sd;
-    a.ddir0 = ddir0;
-    a.flags = work; a.err = work + (size_t)nm * 64;
-    a.sticky = srnn_sticky_flag();
-    SRNN_REQUIRE(a.sticky, "gru_seq: sticky flag allocation failed");
-    a.spin_limit = srnn_persist_spin_limit((int)gseq::SPIN_LIMIT);
-    a.withhold = env_flag("SRNN_PERSIST_FORCE_FAIL", 0);
-    a.B = B; a.D = D; a.Fr = Fr;
-    if (srnn_persist_check((const void*)gru_seq_bwd_kernel, 256, gseqb::LDS,
-                           (int64_t)(D / 16) * nm, "gru_seq_bwd"))
-        return 1;
-    hipLaunchKernelGGL(gru_seq_bwd_kernel, dim3(D / 16, nm), dim3(256), gseqb::LDS, s, a);
-    SRNN_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int srnn_gru_seq_fwd(int dtype, int B, int D, int Fr, const float* gi, int64_t ldgi,
-                                int64_t sgi, const float* h0, const void* h0_lp, const void* whh,
-                                const float* bhh, float* out, void* out_lp, int64_t ldo,
-                                int64_t so, float* gates, int64_t ldg, int64_t sg, int* work,
-                                size_t work_bytes, void* stream) {
-    SRNN_REQUIRE(srnn_gru_seq_supported(dtype, B, D), "gru_seq: shape/device not supported");
+// ------------------------------------------------------------------ host side
+// Work bytes of either direction (64 step flags per row tile, then the error word); 0: the
+// shape or device is not supported.  Every workgroup must be co-resident -- one per CU
+// (160 KiB of LDS each), for every process sharing the device -- and <= 64 unit tiles.
+size_t gru_seq_area(int dtype, int B, int D, int ncu, int share) {
+    if (dtype != SRNN_BF16 || D % 128 != 0 || D > gseq::MAXK || B <= 0 || D / 16 > 64) return 0;
     const int nm = cdiv(B, gseq::BM);
-    const size_t words = (size_t)nm * 64 + 1;
-    SRNN_REQUIRE(work && work_bytes >= words * sizeof(int), "gru_seq: workspace");
-    if (Fr <= 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    SRNN_CHECK_HIP(hipMemsetAsync(work, 0, words * sizeof(int), s));
-    static bool attr = false;
-    if (!attr) {
-        SRNN_CHECK_HIP(hipFuncSetAttribute((const void*)gru_seq_fwd_kernel,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           gseq::LDS));
-        attr = true;
-    }
-    GruSeqArgs a;
-    a.gi = gi; a.ldgi = ldgi; a.sgi = sgi;
-    a.h0 = h0; a.h0_lp = (const bf16*)h0_lp;
-    a.whh = (const bf16*)whh; a.bhh = bhh;
-    a.out = out; a.out_lp = (bf16*)out_lp; a.ldo = ldo; a.so = so;
-    a.gates = gates; a.ldg = ldg; a.sg = sg;
-    a.cnt = work; a.err = work + (size_t)nm * 64;
-    a.sticky = srnn_sticky_flag();
-    SRNN_REQUIRE(a.sticky, "gru_seq: sticky flag allocation failed");
-    a.spin_limit = srnn_persist_spin_limit((int)gseq::SPIN_LIMIT);
-    a.withhold = env_flag("SRNN_PERSIST_FORCE_FAIL", 0);
-    a.B = B; a.D = D; a.Fr = Fr;
-    {
-        const char* e = getenv("SRNN_GSEQ_DIAG");
-        a.diag = e ? atoi(e) : 0;
-    }
-    if (srnn_persist_check((const void*)gru_seq_fwd_kernel, 256, gseq::LDS,
-                           (int64_t)(D / 16) * nm, "gru_seq_fwd"))
-        return 1;
-    hipLaunchKernelGGL(gru_seq_fwd_kernel, dim3(D / 16, nm), dim3(256), gseq::LDS, s, a);
-    SRNN_LAUNCH_CHECK();
-    return 0;
+    if (ncu <= 0 || (int64_t)(D / 16) * nm * share > ncu) return 0;
+    return ((size_t)nm * 64 + 1) * sizeof(int);
 }
+
+int gru_try_seq_fwd(const GruLayerFwd& p, hipStream_t s) {
+    const size_t area = gru_seq_area(p.dtype, p.B, p.D, p.ncu, p.share);
+    if (!area) return -1;
+    SRNN_REQUIRE(p.work && p.work_bytes >= area, "gru_seq: workspace");
+    SRNN_REQUIRE(p.h0_lp && p.out_lp && !p.hprev_lp,
+                 "gru_seq: needs h0_lp and out_lp, writes no hprev_lp");
+    if (p.Fr <= 0) return 0;
+    SRNN_CHECK_HIP(hipMemsetAsync(p.work, 0, area, s));
+    const int nm = cdiv(p.B, gseq::BM);
+    PersistCtl c;
+    if (const int rc = srnn_persist_ctl(c, (int)gseq::SPIN_LIMIT, "gru_seq")) return rc;
+    GruSeqArgs a;
+    a.gi = p.gi; a.ldgi = p.ldgi; a.sgi = p.sgi;
+    a.h0 = p.h0; a.h0_lp = (const bf16*)p.h0_lp;
+    a.whh = (const bf16*)p.whh; a.bhh = p.bhh;
+    a.out = p.out; a.out_lp = (bf16*)p.out_lp; a.ldo = p.ldo; a.so = p.so;
+    a.gates = p.gates; a.ldg = p.ldg; a.sg = p.sg;
+    a.cnt = (int*)p.work; a.err = a.cnt + (size_t)nm * 64;
+    a.sticky = c.sticky; a.spin_limit = c.spin_limit; a.withhold = c.withhold;
+    a.B = p.B; a.D = p.D; a.Fr = p.Fr;
+    a.diag = env_flag("SRNN_GSEQ_DIAG", 0);
+    return srnn_persist_launch((const void*)gru_seq_fwd_kernel, dim3(p.D / 16, nm), 256,
+                               gseq::LDS, gseq::LDS, &a, "gru_seq_fwd", s);
+}
+
+int gru_try_seq_bwd(const GruLayerBwd& p, hipStream_t s) {
+    const size_t area = gru_seq_area(p.dtype, p.B, p.D, p.ncu, p.share);
+    if (!area) return -1;
+    SRNN_REQUIRE(3 * p.D <= gseqb::MAXK && (3 * p.D) % gseqb::R::KB == 0, "gru_seq_bwd: D");
+    SRNN_REQUIRE(p.work && p.work_bytes >= area, "gru_seq_bwd: workspace");
+    SRNN_REQUIRE(p.dgh && p.dgh_lp && p.dgi && !p.dgi_lp && !p.bsum,
+                 "gru_seq_bwd: writes dgh, dgh_lp and dgi, no dgi_lp / bsum");
+    if (p.Fr <= 0) return 0;
+    SRNN_CHECK_HIP(hipMemsetAsync(p.work, 0, area, s));
+    const int nm = cdiv(p.B, gseqb::BM);
+    PersistCtl c;
+    if (const int rc = srnn_persist_ctl(c, (int)gseq::SPIN_LIMIT, "gru_seq")) return rc;
+    GruSeqBwdArgs a;
+    a.dy = p.dy; a.lddy = p.lddy; a.sdy = p.sdy;
+    a.gates = p.gates; a.ldg = p.ldg; a.sg = p.sg;
+    a.hout = p.hout; a.ldo = p.ldo; a.so = p.so; a.h0 = p.h0;
+    a.whh_t = (const bf16*)p.whh_t;
+    a.dgh = p.dgh; a.dgh_lp = (bf16*)p.dgh_lp; a.dgi = p.dgi; a.ldd = p.ldd; a.sd = p.sd;
+    a.ddir0 = p.ddir0;
+    a.flags = (int*)p.work; a.err = a.flags + (size_t)nm * 64;
+    a.sticky = c.sticky; a.spin_limit = c.spin_limit; a.withhold = c.withhold;
+    a.B = p.B; a.D = p.D; a.Fr = p.Fr;
+    return srnn_persist_launch((const void*)gru_seq_bwd_kernel, dim3(p.D / 16, nm), 256,
+                               gseqb::LDS, gseqb::LDS, &a, "gru_seq_bwd", s);
+}
+

@@ -21,6 +21,7 @@
 #include "samplernn_hip_internal.hpp"
 #include "handoff.hpp"
 #include "gru_point.hpp"
+#include "gru_layer.hpp"
 
 namespace gx {
 constexpr int NW = 8, NTHR = NW * 64;
@@ -1055,26 +1056,20 @@ extern "C" int srnn_gru_diag_dump(void) {
     return 0;
 }
 
-// CUs one process's sweep may count on: the device's, divided among the processes that run
-// persistent kernels on it at once (persist.hip, srnn_set_device_share) -- every launch's
-// G x P workgroups then fit beside theirs (handoff.hpp co-residency)
-static int gx_cus() {
-    return srnn_device_cus() / srnn_device_share();
-}
 
-// Row layout of one launch for B rows at width D (GruXArgs): false if the device or shape
-// is not supported.  B beyond what one launch holds (16 MAXMT rows per group) is run as
-// several launches of gx_launch_rows(D) rows each (srnn_gru_xcd_fwd2 / bwd2).
+// Row layout of one launch for B rows at width D (GruXArgs) with `ncu` CUs to count on: the
+// device's, divided among the processes that run persistent kernels on it at once (the
+// plan's ncu / share), so every launch's G x P workgroups fit beside theirs (handoff.hpp
+// co-residency).  false: not supported.  B beyond what one launch holds (16 MAXMT rows per
+// group) runs as several launches of gx_launch_rows rows each.
 struct GxLayout { int mt, G, rv, P; };
 
-static int gx_launch_rows(int D) {
-    const int ncu = gx_cus();
+static int gx_launch_rows(int D, int ncu) {
     if (ncu <= 0 || D % 256 != 0 || D > 1024) return 0;
     return (ncu / (D / gx::CU)) * gx::RG * gx::MAXMT;
 }
 
-static bool gx_layout(int B, int D, GxLayout& L) {
-    const int ncu = gx_cus();
+static bool gx_layout(int B, int D, int ncu, GxLayout& L) {
     if (ncu <= 0 || B <= 0 || D % 256 != 0 || D > 1024) return false;
     L.P = D / gx::CU;
     const int gmax = ncu / L.P;
@@ -1090,57 +1085,54 @@ static bool gx_layout(int B, int D, GxLayout& L) {
     return L.rv <= gx::RG;
 }
 
-// work-buffer bytes of srnn_gru_xcd_fwd for (B, D); 0 if the shape / device is not supported
-extern "C" size_t srnn_gru_xcd_work_bytes(int dtype, int B, int D) {
-    if (dtype != SRNN_BF16 || B <= 0) return 0;
-    const int lr = gx_launch_rows(D);
+// work bytes: header (error word first, census) + two generations of hand-off granules, `gw`
+// 8-byte granules per row, for the rows of one launch; 0 if the shape / device is not supported
+static size_t gx_area(int dtype, int B, int D, int ncu, int share, int gw) {
+    if (dtype != SRNN_BF16 || B <= 0 || share < 1) return 0;
+    const int lr = gx_launch_rows(D, ncu / share);
     GxLayout L;
-    if (lr <= 0 || !gx_layout(B < lr ? B : lr, D, L)) return 0;
-    return gx::HDR + (size_t)2 * L.G * L.mt * gx::RG * (D / 2) * 8;
+    if (lr <= 0 || !gx_layout(B < lr ? B : lr, D, ncu / share, L)) return 0;
+    return gx::HDR + (size_t)2 * L.G * L.mt * gx::RG * gw * 8;
 }
 
-extern "C" int srnn_gru_xcd_fwd2(int dtype, int B, int D, int Fr, const float* gi, int64_t ldgi,
-                                 int64_t sgi, const float* h0, const void* whh, const float* bhh,
-                                 float* out, void* out_lp, int64_t ldo, int64_t so, float* gates,
-                                 int64_t ldg, int64_t sg, void* hprev_lp, void* work,
-                                 size_t work_bytes, void* stream) {
-    const size_t need = srnn_gru_xcd_work_bytes(dtype, B, D);
-    SRNN_REQUIRE(need > 0, "gru_xcd: shape/device not supported");
-    SRNN_REQUIRE(work && work_bytes >= need, "gru_xcd: workspace %zu < %zu", work_bytes, need);
+size_t gru_xcd_fwd_area(int dtype, int B, int D, int ncu, int share) {
+    return gx_area(dtype, B, D, ncu, share, D / 2);
+}
+
+size_t gru_xcd_bwd_area(int dtype, int B, int D, int ncu, int share) {
+    return gx_area(dtype, B, D, ncu, share, 3 * D / 2);
+}
+
+int gru_try_xcd_fwd(const GruLayerFwd& p, hipStream_t s) {
+    const int B = p.B, D = p.D, Fr = p.Fr;
+    const size_t need = gru_xcd_fwd_area(p.dtype, B, D, p.ncu, p.share);
+    if (!need) return -1;
+    SRNN_REQUIRE(p.work && p.work_bytes >= need, "gru_xcd: workspace %zu < %zu", p.work_bytes,
+                 need);
     if (Fr <= 0) return 0;
-    const int lr = gx_launch_rows(D);
+    const int lr = gx_launch_rows(D, p.ncu / p.share);
     if (B > lr) {     // rows are independent: consecutive launches over row chunks
-        for (int c = 0; c < B; c += lr) {
-            const int n = B - c < lr ? B - c : lr;
-            const int rc = srnn_gru_xcd_fwd2(
-                dtype, n, D, Fr, gi + (int64_t)c * ldgi, ldgi, sgi, h0 + (int64_t)c * D, whh,
-                bhh, out + (int64_t)c * ldo, (bf16*)out_lp + (int64_t)c * ldo, ldo, so,
-                gates + (int64_t)c * ldg, ldg, sg,
-                hprev_lp ? (void*)((bf16*)hprev_lp + (int64_t)c * ldo) : nullptr, work,
-                work_bytes, stream);
-            if (rc) return rc;
-        }
+        for (int c = 0; c < B; c += lr)
+            if (const int rc = gru_try_xcd_fwd(p.rows(c, B - c < lr ? B - c : lr), s)) return rc;
         return 0;
     }
     GxLayout L;
-    SRNN_REQUIRE(gx_layout(B, D, L), "gru_xcd: no row layout for B=%d D=%d", B, D);
-    hipStream_t s = (hipStream_t)stream;
+    SRNN_REQUIRE(gx_layout(B, D, p.ncu / p.share, L), "gru_xcd: no row layout for B=%d D=%d", B, D);
     // granules, census and error word start zeroed every call (tags count from 1)
-    SRNN_CHECK_HIP(hipMemsetAsync(work, 0, need, s));
+    SRNN_CHECK_HIP(hipMemsetAsync(p.work, 0, need, s));
+    PersistCtl c;
+    if (const int rc = srnn_persist_ctl(c, hx::SPIN_LIMIT, "gru_xcd")) return rc;
     GruXArgs a;
-    a.gi = gi; a.ldgi = ldgi; a.sgi = sgi;
-    a.h0 = h0; a.whh = (const bf16*)whh; a.bhh = bhh;
-    a.out = out; a.out_lp = (bf16*)out_lp; a.ldo = ldo; a.so = so;
-    a.hp_lp = (bf16*)hprev_lp;
-    a.gates = gates; a.ldg = ldg; a.sg = sg;
-    a.err = (int*)work;
-    a.sticky = srnn_sticky_flag();
-    SRNN_REQUIRE(a.sticky, "gru_xcd: sticky flag allocation failed");
-    a.spin_limit = srnn_persist_spin_limit(hx::SPIN_LIMIT);
-    a.withhold = env_flag("SRNN_PERSIST_FORCE_FAIL", 0);
-    a.census = (int*)work + 16;
+    a.gi = p.gi; a.ldgi = p.ldgi; a.sgi = p.sgi;
+    a.h0 = p.h0; a.whh = (const bf16*)p.whh; a.bhh = p.bhh;
+    a.out = p.out; a.out_lp = (bf16*)p.out_lp; a.ldo = p.ldo; a.so = p.so;
+    a.hp_lp = (bf16*)p.hprev_lp;
+    a.gates = p.gates; a.ldg = p.ldg; a.sg = p.sg;
+    a.err = (int*)p.work;
+    a.sticky = c.sticky; a.spin_limit = c.spin_limit; a.withhold = c.withhold;
+    a.census = (int*)p.work + 16;
     a.nolocal = !env_flag("SRNN_GEN_LOCAL", 1);
-    a.xh = (u64*)((char*)work + gx::HDR);
+    a.xh = (u64*)((char*)p.work + gx::HDR);
     a.B = B; a.D = D; a.Fr = Fr;
     a.diag = nullptr;
     a.poll_sleep = env_flag("SRNN_POLL_SLEEP", 1);
@@ -1173,99 +1165,56 @@ extern "C" int srnn_gru_xcd_fwd2(int dtype, int B, int D, int Fr, const float* g
     static const FwdK k1024[3] = {gru_xcd_fwd_kernel<4, 1, 1024>, gru_xcd_fwd_kernel<4, 2, 1024>,
                                   gru_xcd_fwd_kernel<4, 4, 1024>};
     const FwdK k = D == 1024 && env_flag("SRNN_GX_DC", 1) ? k1024[mi] : ks[ui][mi];
-    static bool attr[4][3] = {};
-    const int ai = k == ks[ui][mi] ? ui : 3;
-    if (!attr[ai][mi]) {
-        SRNN_CHECK_HIP(hipFuncSetAttribute((const void*)k,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           160 * 1024));
-        attr[ai][mi] = true;
-    }
-    if (srnn_persist_check((const void*)k, gx::NTHR, lds, (int64_t)a.G * a.P, "gru_xcd_fwd"))
-        return 1;
-    hipLaunchKernelGGL(k, dim3(a.G * a.P), dim3(gx::NTHR), lds, s, a);
-    SRNN_LAUNCH_CHECK();
-    return 0;
+    return srnn_persist_launch((const void*)k, dim3(a.G * a.P), gx::NTHR, lds, 160 * 1024, &a,
+                               "gru_xcd_fwd", s);
 }
 
-extern "C" int srnn_gru_xcd_fwd(int dtype, int B, int D, int Fr, const float* gi, int64_t ldgi,
-                                int64_t sgi, const float* h0, const void* whh, const float* bhh,
-                                float* out, void* out_lp, int64_t ldo, int64_t so, float* gates,
-                                int64_t ldg, int64_t sg, void* work, size_t work_bytes,
-                                void* stream) {
-    return srnn_gru_xcd_fwd2(dtype, B, D, Fr, gi, ldgi, sgi, h0, whh, bhh, out, out_lp, ldo, so,
-                             gates, ldg, sg, nullptr, work, work_bytes, stream);
-}
-
-
-// work-buffer bytes of srnn_gru_xcd_bwd for (B, D); 0 if not supported
-extern "C" size_t srnn_gru_xcd_bwd_work_bytes(int dtype, int B, int D) {
-    if (!srnn_gru_xcd_work_bytes(dtype, B, D)) return 0;
-    const int lr = gx_launch_rows(D);
-    GxLayout L;
-    if (!gx_layout(B < lr ? B : lr, D, L)) return 0;
-    return gx::HDR + (size_t)2 * L.G * L.mt * gx::RG * (3 * D / 2) * 8;
-}
-
-extern "C" int srnn_gru_xcd_bwd2(int dtype, int B, int D, int Fr, const float* dy, int64_t lddy,
-                                 int64_t sdy, const float* gates, int64_t ldg, int64_t sg,
-                                 const float* hout, int64_t ldo, int64_t so, const float* h0,
-                                 const void* whh_t, float* dgh, void* dgh_lp, float* dgi,
-                                 void* dgi_lp, float* bsum, int64_t ldd, int64_t sd, float* ddir0,
-                                 void* work, size_t work_bytes, void* stream) {
-    const size_t need = srnn_gru_xcd_bwd_work_bytes(dtype, B, D);
-    SRNN_REQUIRE(need > 0, "gru_xcd_bwd: shape/device not supported");
-    SRNN_REQUIRE(work && work_bytes >= need, "gru_xcd_bwd: workspace %zu < %zu", work_bytes, need);
-    SRNN_REQUIRE(dgh_lp, "gru_xcd_bwd: dgh_lp is required");
+int gru_try_xcd_bwd(const GruLayerBwd& p, hipStream_t s) {
+    const int B = p.B, D = p.D, Fr = p.Fr;
+    const size_t need = gru_xcd_bwd_area(p.dtype, B, D, p.ncu, p.share);
+    if (!need) return -1;
+    SRNN_REQUIRE(p.work && p.work_bytes >= need, "gru_xcd_bwd: workspace %zu < %zu", p.work_bytes,
+                 need);
+    SRNN_REQUIRE(p.dgh_lp, "gru_xcd_bwd: dgh_lp is required");
     if (Fr <= 0) return 0;
-    const int lr = gx_launch_rows(D);
+    const int lr = gx_launch_rows(D, p.ncu / p.share);
     if (B > lr) {     // rows are independent: consecutive launches over row chunks
-        for (int c = 0; c < B; c += lr) {
-            const int n = B - c < lr ? B - c : lr;
-            const int rc = srnn_gru_xcd_bwd2(
-                dtype, n, D, Fr, dy + (int64_t)c * lddy, lddy, sdy, gates + (int64_t)c * ldg,
-                ldg, sg, hout + (int64_t)c * ldo, ldo, so, h0 + (int64_t)c * D, whh_t,
-                dgh ? dgh + (int64_t)c * ldd : nullptr, (bf16*)dgh_lp + (int64_t)c * ldd,
-                dgi ? dgi + (int64_t)c * ldd : nullptr,
-                dgi_lp ? (void*)((bf16*)dgi_lp + (int64_t)c * ldd) : nullptr,
-                bsum ? bsum + (int64_t)c * 4 * D : nullptr, ldd, sd, ddir0 + (int64_t)c * D,
-                work, work_bytes, stream);
-            if (rc) return rc;
-        }
+        for (int c = 0; c < B; c += lr)
+            if (const int rc = gru_try_xcd_bwd(p.rows(c, B - c < lr ? B - c : lr), s)) return rc;
         return 0;
     }
     GxLayout L;
-    SRNN_REQUIRE(gx_layout(B, D, L), "gru_xcd_bwd: no row layout for B=%d D=%d", B, D);
-    hipStream_t s = (hipStream_t)stream;
+    SRNN_REQUIRE(gx_layout(B, D, p.ncu / p.share, L), "gru_xcd_bwd: no row layout for B=%d D=%d", B,
+                 D);
     // packed hand-off form (gru_xcd_bwd_pk_kernel): one {3 x bf16, tag} granule per unit;
     // tags (<= Fr) must stay finite bf16 patterns (< 0x7f80); SRNN_GX_PK=0 restores the form
     // with {2 x bf16, 32-bit tag} granules
     // (the packed kernel's operand fetch uses 32-bit buffer offsets: a launch with any byte
     //  offset past 2 GB -- very long sequences -- takes the unpacked kernel's 64-bit pointers)
-    const int64_t omax = std::max({((int64_t)(B - 1) * lddy + (int64_t)(Fr - 1) * sdy + D) * 4,
-                                   ((int64_t)(B - 1) * ldg + (int64_t)(Fr - 1) * sg + 4 * D) * 4,
-                                   ((int64_t)(B - 1) * ldo + (int64_t)(Fr - 1) * so + D) * 4,
-                                   (int64_t)B * D * 4});
+    const int64_t omax =
+        std::max({((int64_t)(B - 1) * p.lddy + (int64_t)(Fr - 1) * p.sdy + D) * 4,
+                  ((int64_t)(B - 1) * p.ldg + (int64_t)(Fr - 1) * p.sg + 4 * D) * 4,
+                  ((int64_t)(B - 1) * p.ldo + (int64_t)(Fr - 1) * p.so + D) * 4,
+                  (int64_t)B * D * 4});
     const bool pk = D % 64 == 0 && D / 64 <= 16 && (D / 64) % 4 == 0 && Fr < 0x7f80 &&
                     omax < 0x7fffffffll - 64 && env_flag("SRNN_GX_PK", 1);
     const size_t clear = pk ? gx::HDR + (size_t)2 * L.G * L.mt * gx::RG * D * 8 : need;
-    SRNN_CHECK_HIP(hipMemsetAsync(work, 0, clear, s));
+    SRNN_CHECK_HIP(hipMemsetAsync(p.work, 0, clear, s));
+    PersistCtl c;
+    if (const int rc = srnn_persist_ctl(c, hx::SPIN_LIMIT, "gru_xcd_bwd")) return rc;
     GruXBwdArgs a;
-    a.dy = dy; a.lddy = lddy; a.sdy = sdy;
-    a.gates = gates; a.ldg = ldg; a.sg = sg;
-    a.hout = hout; a.ldo = ldo; a.so = so; a.h0 = h0;
-    a.whh_t = (const bf16*)whh_t;
-    a.dgh = dgh; a.dgh_lp = (bf16*)dgh_lp; a.dgi = dgi; a.ldd = ldd; a.sd = sd;
-    a.dgi_lp = (bf16*)dgi_lp; a.bsum = bsum;
-    a.ddir0 = ddir0;
-    a.err = (int*)work;
-    a.sticky = srnn_sticky_flag();
-    SRNN_REQUIRE(a.sticky, "gru_xcd_bwd: sticky flag allocation failed");
-    a.spin_limit = srnn_persist_spin_limit(hx::SPIN_LIMIT);
-    a.withhold = env_flag("SRNN_PERSIST_FORCE_FAIL", 0);
-    a.census = (int*)work + 16;
+    a.dy = p.dy; a.lddy = p.lddy; a.sdy = p.sdy;
+    a.gates = p.gates; a.ldg = p.ldg; a.sg = p.sg;
+    a.hout = p.hout; a.ldo = p.ldo; a.so = p.so; a.h0 = p.h0;
+    a.whh_t = (const bf16*)p.whh_t;
+    a.dgh = p.dgh; a.dgh_lp = (bf16*)p.dgh_lp; a.dgi = p.dgi; a.ldd = p.ldd; a.sd = p.sd;
+    a.dgi_lp = (bf16*)p.dgi_lp; a.bsum = p.bsum;
+    a.ddir0 = p.ddir0;
+    a.err = (int*)p.work;
+    a.sticky = c.sticky; a.spin_limit = c.spin_limit; a.withhold = c.withhold;
+    a.census = (int*)p.work + 16;
     a.nolocal = !env_flag("SRNN_GEN_LOCAL", 1);
-    a.xg = (u64*)((char*)work + gx::HDR);
+    a.xg = (u64*)((char*)p.work + gx::HDR);
     a.B = B; a.D = D; a.Fr = Fr;
     a.exp = env_flag("SRNN_GX_EXP", 0);
     a.G = L.G;
@@ -1275,12 +1224,13 @@ extern "C" int srnn_gru_xcd_bwd2(int dtype, int B, int D, int Fr, const float* d
     const int KW = pk ? gx::NW : NU < gx::NW ? NU : gx::NW;
     size_t lds = (size_t)2 * KW * 2 * 4 * gx::PS * 4 + 64 +
                  (L.mt > 1 ? (size_t)L.mt * 5 * gx::NTHR * 4 : 0);
+    const int mi = L.mt == 1 ? 0 : L.mt == 2 ? 1 : 2;
+    typedef void (*BwdK)(GruXBwdArgs);
     if (pk) {
         // (the prologue stages 32 W_hh^T rows of one gate in the same dynamic LDS)
         const size_t stage = (size_t)32 * (2 * D + 16);
         if (lds < stage) lds = stage;
-        typedef void (*PkK)(GruXBwdArgs);
-        static const PkK kp[4][3] = {
+        static const BwdK kp[4][3] = {
             {gru_xcd_bwd_pk_kernel<4, 1>, gru_xcd_bwd_pk_kernel<4, 2>, gru_xcd_bwd_pk_kernel<4, 4>},
             {gru_xcd_bwd_pk_kernel<8, 1>, gru_xcd_bwd_pk_kernel<8, 2>, gru_xcd_bwd_pk_kernel<8, 4>},
             {gru_xcd_bwd_pk_kernel<12, 1>, gru_xcd_bwd_pk_kernel<12, 2>,
@@ -1290,33 +1240,20 @@ extern "C" int srnn_gru_xcd_bwd2(int dtype, int B, int D, int Fr, const float* d
         // MT > 1: the batched form (two tiles per phase: 11.5 -> 8.9 us per step at 512 rows;
         // SRNN_GX_BATCH=0: one tile per phase, for A/B and tests); its reduction buffers hold
         // two tiles' partials
-        static const PkK kpb[4][3] = {
+        static const BwdK kpb[4][3] = {
             {nullptr, gru_xcd_bwd_pk_kernel<4, 2, 2>, gru_xcd_bwd_pk_kernel<4, 4, 2>},
             {nullptr, gru_xcd_bwd_pk_kernel<8, 2, 2>, gru_xcd_bwd_pk_kernel<8, 4, 2>},
             {nullptr, gru_xcd_bwd_pk_kernel<12, 2, 2>, gru_xcd_bwd_pk_kernel<12, 4, 2>},
             {nullptr, gru_xcd_bwd_pk_kernel<16, 2, 2>, gru_xcd_bwd_pk_kernel<16, 4, 2>}};
-        const int mi = L.mt == 1 ? 0 : L.mt == 2 ? 1 : 2;
-        const int bi = kpb[D / 256 - 1][mi] && env_flag("SRNN_GX_BATCH", 1) ? 1 : 0;
-        const PkK k = bi ? kpb[D / 256 - 1][mi] : kp[D / 256 - 1][mi];
-        if (bi) lds += (size_t)2 * KW * 2 * 4 * gx::PS * 4;
-        static bool attr[2][4][3] = {};
-        if (!attr[bi][D / 256 - 1][mi]) {
-            SRNN_CHECK_HIP(hipFuncSetAttribute((const void*)k,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               160 * 1024));
-            attr[bi][D / 256 - 1][mi] = true;
-        }
-        if (srnn_persist_check((const void*)k, gx::NTHR, lds, (int64_t)a.G * a.P, "gru_xcd_bwd"))
-            return 1;
-        hipLaunchKernelGGL(k, dim3(a.G * a.P), dim3(gx::NTHR), lds, s, a);
-        SRNN_LAUNCH_CHECK();
-        return 0;
+        const bool batch = kpb[D / 256 - 1][mi] && env_flag("SRNN_GX_BATCH", 1);
+        if (batch) lds += (size_t)2 * KW * 2 * 4 * gx::PS * 4;
+        const BwdK k = batch ? kpb[D / 256 - 1][mi] : kp[D / 256 - 1][mi];
+        return srnn_persist_launch((const void*)k, dim3(a.G * a.P), gx::NTHR, lds, 160 * 1024, &a,
+                                   "gru_xcd_bwd", s);
     }
     const int upw = cdiv(NU, gx::NW);
     const int ui = upw <= 3 ? 0 : upw <= 6 ? 1 : 2;
     const bool full = NU == (ui == 0 ? 3 : ui == 1 ? 6 : 12) * gx::NW;
-    const int mi = L.mt == 1 ? 0 : L.mt == 2 ? 1 : 2;
-    typedef void (*BwdK)(GruXBwdArgs);
     // FULL holds for D = 256 / 512 / 1024 (UPW = 3 / 6 / 12); D = 768 takes the UPW = 12 form
     static const BwdK ks[2][3][3] = {
         {{nullptr, nullptr, nullptr},
@@ -1331,25 +1268,12 @@ extern "C" int srnn_gru_xcd_bwd2(int dtype, int B, int D, int Fr, const float* d
           gru_xcd_bwd_kernel<12, true, 4>}}};
     const BwdK k = ks[full ? 1 : 0][ui][mi];
     SRNN_REQUIRE(k, "gru_xcd_bwd: no kernel for D=%d", D);
-    if (srnn_persist_check((const void*)k, gx::NTHR, lds, (int64_t)a.G * a.P, "gru_xcd_bwd"))
-        return 1;
-    hipLaunchKernelGGL(k, dim3(a.G * a.P), dim3(gx::NTHR), lds, s, a);
-    SRNN_LAUNCH_CHECK();
-    return 0;
+    // (this form's LDS fits the default limit: not raised)
+    return srnn_persist_launch((const void*)k, dim3(a.G * a.P), gx::NTHR, lds, 0, &a,
+                               "gru_xcd_bwd", s);
 }
 
-extern "C" int srnn_gru_xcd_bwd(int dtype, int B, int D, int Fr, const float* dy, int64_t lddy,
-                                int64_t sdy, const float* gates, int64_t ldg, int64_t sg,
-                                const float* hout, int64_t ldo, int64_t so, const float* h0,
-                                const void* whh_t, float* dgh, void* dgh_lp, float* dgi,
-                                int64_t ldd, int64_t sd, float* ddir0, void* work,
-                                size_t work_bytes, void* stream) {
-    return srnn_gru_xcd_bwd2(dtype, B, D, Fr, dy, lddy, sdy, gates, ldg, sg, hout, ldo, so, h0,
-                             whh_t, dgh, dgh_lp, dgi, nullptr, nullptr, ldd, sd, ddir0, work,
-                             work_bytes, stream);
-}
-
-// nonzero if the previous srnn_gru_xcd_fwd/bwd on `work` gave up a hand-off (synchronises)
+// nonzero if the previous XCD sweep on `work` gave up a hand-off (synchronises)
 extern "C" int srnn_gru_xcd_error(const void* work) {
     int e = 0;
     if (hipMemcpy(&e, work, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return -1;

@@ -90,6 +90,32 @@ int srnn_persist_check(const void* kernel, int threads, size_t lds, int64_t bloc
     return 0;
 }
 
+int srnn_raise_lds(const void* kernel, int bytes) {
+    static std::unordered_set<const void*> raised;
+    if (raised.count(kernel)) return 0;
+    SRNN_CHECK_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    raised.insert(kernel);
+    return 0;
+}
+
+int srnn_persist_ctl(PersistCtl& c, int spin_dflt, const char* what) {
+    c.sticky = srnn_sticky_flag();
+    SRNN_REQUIRE(c.sticky, "%s: sticky flag allocation failed", what);
+    c.spin_limit = srnn_persist_spin_limit(spin_dflt);
+    c.withhold = env_flag("SRNN_PERSIST_FORCE_FAIL", 0);
+    return 0;
+}
+
+int srnn_persist_launch(const void* kernel, dim3 grid, int threads, size_t lds, int lds_limit,
+                        void* args, const char* what, hipStream_t s) {
+    if (lds_limit)
+        if (const int rc = srnn_raise_lds(kernel, lds_limit)) return rc;
+    if (srnn_persist_check(kernel, threads, lds, (int64_t)grid.x * grid.y, what)) return 1;
+    SRNN_CHECK_HIP(hipLaunchKernel(kernel, grid, dim3(threads), &args, lds, s));
+    SRNN_LAUNCH_CHECK();
+    return 0;
+}
+
 // Diagnostics / tests: occupy `blocks` CUs (a full 160 KiB of LDS each, so one workgroup
 // per CU) for `usec` microseconds of wall time -- the "other work holding CUs when a
 // persistent grid starts" of the co-residency tests (tests/test_gpu_coresidency.py).
@@ -105,13 +131,7 @@ __global__ void hold_cus_kernel(unsigned long long ticks, int* done) {
 
 extern "C" int srnn_hold_cus(int blocks, int usec, int* done, void* stream) {
     SRNN_REQUIRE(blocks > 0 && usec >= 0 && usec <= 10000000, "hold_cus: bad arguments");
-    static bool attr = false;
-    if (!attr) {
-        SRNN_CHECK_HIP(hipFuncSetAttribute((const void*)hold_cus_kernel,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           160 * 1024));
-        attr = true;
-    }
+    if (const int rc = srnn_raise_lds((const void*)hold_cus_kernel, 160 * 1024)) return rc;
     hipLaunchKernelGGL(hold_cus_kernel, dim3(blocks), dim3(64), 160 * 1024, (hipStream_t)stream,
                        (unsigned long long)usec * 100ull, done);
     SRNN_LAUNCH_CHECK();
@@ -196,13 +216,5 @@ extern "C" int srnn_persistent_flag_or(const void* src, int dtype, void* stream)
     hipLaunchKernelGGL(flag_or_bf16_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, f,
                        (const bf16*)src);
     SRNN_LAUNCH_CHECK();
-    return 0;
-}
-
-int srnn_raise_lds(const void* kernel, int bytes) {
-    static std::unordered_set<const void*> raised;
-    if (raised.count(kernel)) return 0;
-    SRNN_CHECK_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    raised.insert(kernel);
     return 0;
 }

@@ -46,6 +46,15 @@ extern "C" int srnn_device_share(void);
 int srnn_persist_fits_cus(int64_t blocks);
 int srnn_persist_check(const void* kernel, int threads, size_t lds, int64_t blocks,
                        const char* what);
+// persist.hip: what every persistent kernel's argument block copies -- the sticky flag, the
+// spin limit (dflt, or the test switch's short one) and the SRNN_PERSIST_FORCE_FAIL withhold
+// switch; an error when the flag cannot be allocated
+struct PersistCtl { int* sticky; int spin_limit; int withhold; };
+int srnn_persist_ctl(PersistCtl& c, int spin_dflt, const char* what);
+// persist.hip: launch of a persistent kernel taking the one argument block *args -- raise its
+// dynamic LDS limit to lds_limit (0: leave it), srnn_persist_check for the grid, launch, check
+int srnn_persist_launch(const void* kernel, dim3 grid, int threads, size_t lds, int lds_limit,
+                        void* args, const char* what, hipStream_t s);
 
 // gemm3.hip: grow-only device scratch buffers, one per slot, never freed (a captured HIP graph
 // keeps the pointer current at its capture); null on a HIP error.  Allocated on first use,

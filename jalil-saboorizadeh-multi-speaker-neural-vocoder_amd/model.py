@@ -289,6 +289,74 @@ class _State:
     """What a tier / MLP forward keeps for its backward (custom_ops stash)."""
 
 
+def _gru_layer_forward(T, B, D, Fr, gi, h0, whh, b_hh):
+    """One GRU layer over all Fr steps (srnn_gru_layer_fwd: the library plans the back end --
+    a persistent sweep or one cell launch per step).  gi (B*Fr, 3D) fp32, h0 (B, D) fp32.
+    Returns out (fp32), its T copy (out itself in fp32), the saved gates, and -- from the XCD
+    sweep only, else None -- the previous-state sequence [h0, h_0 .. h_{F-2}] in T that the
+    backward's W_hh gradient consumes."""
+    dev = gi.device
+    lp = T != torch.float32
+    be, nwork, _ = H.gru_layer_plan(T, B, D)
+    out = torch.empty((B, Fr, D), device=dev, dtype=torch.float32)
+    outT = torch.empty((B, Fr, D), device=dev, dtype=T) if lp else out
+    gt = torch.empty((B, Fr, 4 * D), device=dev, dtype=torch.float32)
+    hprevT = torch.empty((B, Fr, D), device=dev, dtype=T) if be == 'xcd' else None
+    work = torch.empty(nwork, device=dev, dtype=torch.uint8) if nwork else None
+    if be != 'steps':
+        H.before_persistent_sweep()
+    _STATS[{'xcd': 'gru_xcd_fwd', 'seq': 'gru_seq', 'steps': 'gru_cell_steps'}[be]] += \
+        Fr if be == 'steps' else 1
+    ev = H.roof_begin() if be == 'xcd' else None
+    H.lib().call('srnn_gru_layer_fwd', H.dcode(T), B, D, Fr, H.ptr(gi), Fr * 3 * D, 3 * D,
+                 H.ptr(h0), H.ptr(whh), H.ptr(b_hh), H.ptr(out), H.ptr(outT) if lp else None,
+                 Fr * D, D, H.ptr(gt), Fr * 4 * D, 4 * D, H.ptr(hprevT), H.ptr(work), nwork,
+                 H.stream())
+    H.roof_end('gru_xcd_fwd', ev, 2.0 * B * Fr * 3 * D * D)
+    return out, outT, gt, hprevT
+
+
+def _gru_layer_backward(T, B, D, Fr, dOut, gates, out, h0, whh, whhT):
+    """Reverse sweep of one GRU layer (srnn_gru_layer_bwd, the same plan as the forward).
+    Returns (dGH, dGHT, dGI, dGIT, bsum, ddir0) in one of two forms.  Under the XCD plan the
+    sweep writes the GEMM operands dGHT / dGIT (T) and per-row bias sums bsum (B, 4D), no
+    fp32 copies of either (dGH, dGI None); under the others fp32 dGH / dGI and dGHT (the T
+    copy of dGH; dGH itself in fp32), with dGIT and bsum None.  ddir0: dh_direct of step 0."""
+    dev = dOut.device
+    lp = T != torch.float32
+    be, _, nwork = H.gru_layer_plan(T, B, D)
+    g3 = (B, Fr, 3 * D)
+    dGH = dGI = dGIT = bsum = None
+    if be == 'xcd':
+        dGHT = torch.empty(g3, device=dev, dtype=T)
+        dGIT = torch.empty(g3, device=dev, dtype=T)
+        bsum = torch.empty((B, 4 * D), device=dev, dtype=torch.float32)
+    else:
+        dGH = torch.empty(g3, device=dev, dtype=torch.float32)
+        dGHT = torch.empty(g3, device=dev, dtype=T) if lp else dGH
+        dGI = torch.empty(g3, device=dev, dtype=torch.float32)
+    ddir0 = torch.empty((B, D), device=dev, dtype=torch.float32)
+    work = torch.empty(nwork, device=dev, dtype=torch.uint8) if nwork else None
+    dOut = dOut.contiguous()
+    if be != 'steps':
+        H.before_persistent_sweep()       # (DP: in-flight all-reduces finish first)
+    else:
+        _STATS['gru_cell_bwd_steps'] += Fr
+    ev = None
+    if be == 'xcd':
+        _STATS['gru_xcd_bwd'] += 1
+        ev = H.roof_begin()
+    H.lib().call('srnn_gru_layer_bwd', H.dcode(T), B, D, Fr, H.ptr(dOut), Fr * D, D,
+                 H.ptr(gates), Fr * 4 * D, 4 * D, H.ptr(out), Fr * D, D, H.ptr(h0), H.ptr(whh),
+                 H.ptr(whhT), H.ptr(dGH), H.ptr(dGHT) if lp else None, H.ptr(dGI), H.ptr(dGIT),
+                 H.ptr(bsum), Fr * 3 * D, 3 * D, H.ptr(ddir0), H.ptr(work), nwork, H.stream())
+    # (the dgh_{t+1} W_hh products of steps 1 .. F-1; step F-1 has none)
+    H.roof_end('gru_xcd_bwd', ev, 2.0 * B * (Fr - 1) * 3 * D * D)
+    if be != 'steps':
+        H.after_persistent_sweep()        # (DP: gradient buckets ready before it go out now)
+    return dGH, dGHT, dGI, dGIT, bsum, ddir0
+
+
 def tier_forward(mod, prev, upper, cond, spk, hidden, h0, ps):
     """FrameLevelRNN forward (model.py:180-263) on the HIP kernels: returns (Y, h_new, state)
     with state what tier_backward needs (srnn::tier_fwd, custom_ops.py)."""
@@ -359,49 +427,7 @@ def tier_forward(mod, prev, upper, cond, spk, hidden, h0, ps):
         bhh.append(b_hh)
         XT = H.cast(X, T)
         gi = H.linear(XT, Wih[l], bias=b_ih)                      # (B*F, 3D)
-        out = torch.empty((B, Fr, D), device=dev, dtype=torch.float32)
-        outT = torch.empty((B, Fr, D), device=dev, dtype=T) if lp else out
-        gt = torch.empty((B, Fr, 4 * D), device=dev, dtype=torch.float32)
-        hpf = h_in[l]
-        xw = H.gru_xcd_work_bytes(T, B, D) if lp else 0
-        # (the XCD sweep reads the fp32 state itself; the other paths take a T copy)
-        hpT = H.cast(hpf, T) if xw == 0 else None
-        seq = lp and (xw > 0 or H.gru_seq_supported(T, B, D))
-        if seq:
-            H.before_persistent_sweep()
-        hprevT = None
-        if xw > 0:
-            # whole sequence in one persistent launch, row groups per XCD, W_hh in VGPRs;
-            # it also writes the previous-state sequence [h0, h_0 .. h_{F-2}] in bf16 for
-            # the backward's W_hh gradient
-            work = torch.empty(xw, device=dev, dtype=torch.uint8)
-            hprevT = torch.empty((B, Fr, D), device=dev, dtype=T)
-            _STATS['gru_xcd_fwd'] += 1
-            ev = H.roof_begin()
-            H.lib().call('srnn_gru_xcd_fwd2', H.dcode(T), B, D, Fr, H.ptr(gi), Fr * 3 * D,
-                         3 * D, H.ptr(hpf), H.ptr(Whh[l]), H.ptr(b_hh), H.ptr(out),
-                         H.ptr(outT), Fr * D, D, H.ptr(gt), Fr * 4 * D, 4 * D,
-                         H.ptr(hprevT), H.ptr(work), xw, H.stream())
-            H.roof_end('gru_xcd_fwd', ev, 2.0 * B * Fr * 3 * D * D)
-        elif seq:
-            # whole sequence in one persistent launch (W_hh resident in LDS)
-            work = torch.empty(64 * ((B + 31) // 32) + 1, device=dev, dtype=torch.int32)
-            _STATS['gru_seq'] += 1
-            H.lib().call('srnn_gru_seq_fwd', H.dcode(T), B, D, Fr, H.ptr(gi), Fr * 3 * D,
-                         3 * D, H.ptr(hpf), H.ptr(hpT), H.ptr(Whh[l]), H.ptr(b_hh),
-                         H.ptr(out), H.ptr(outT), Fr * D, D, H.ptr(gt), Fr * 4 * D, 4 * D,
-                         H.ptr(work), work.numel() * 4, H.stream())
-        _STATS['gru_cell_steps'] += 0 if seq else Fr
-        for t in range(0 if not seq else Fr, Fr):
-            if t == 0:
-                hp_t, hp_f, ldh = hpT, hpf, D
-            else:
-                hp_t, hp_f, ldh = outT[:, t - 1], out[:, t - 1], Fr * D
-            H.lib().call('srnn_gru_cell', H.dcode(T), B, D, D, None, 0, None, None,
-                         H.ptr(gi[t:]), Fr * 3 * D, H.ptr(hp_t), ldh, H.ptr(hp_f), ldh,
-                         H.ptr(Whh[l]), H.ptr(b_hh), H.ptr(out[:, t]), Fr * D,
-                         H.ptr(outT[:, t]) if lp else None, Fr * D, H.ptr(gt[:, t]),
-                         Fr * 4 * D, H.stream())
+        out, outT, gt, hprevT = _gru_layer_forward(T, B, D, Fr, gi, h_in[l], Whh[l], b_hh)
         xs.append(XT)
         hprevs.append(hprevT)
         outs.append(out)
@@ -481,64 +507,11 @@ def tier_backward(ctx, dY, need_h0):
         # W_hh^T (D, 3D): k-contiguous operand for the deep-ring backward kernel, straight
         # from the fp32 parameter (the same bf16 values as the forward's copy, no cast pass)
         WhhT = H.permute3(WhhF[l].detach().reshape(1, 3 * D, D), (0, 2, 1), dtype=T)
-        xbw = H.gru_xcd_bwd_work_bytes(T, B, D) if lp else 0
-        seq = lp and (xbw > 0 or H.gru_seq_supported(T, B, D))
-        ddir = [torch.empty((B, D), device=dev, dtype=torch.float32) for _ in range(2)]
-        dGIT = bsum = None
-        if xbw > 0:
-            # the sweep writes bf16 dgh / dgi (the GEMM operands) and per-row bias sums;
-            # no fp32 copies of either
-            dGH = dGI = None
-            dGHT = torch.empty((B, Fr, 3 * D), device=dev, dtype=T)
-            dGIT = torch.empty((B, Fr, 3 * D), device=dev, dtype=T)
-            bsum = torch.empty((B, 4 * D), device=dev, dtype=torch.float32)
-        else:
-            dGH = torch.empty((B, Fr, 3 * D), device=dev, dtype=torch.float32)
-            dGHT = torch.empty((B, Fr, 3 * D), device=dev, dtype=T) if lp else dGH
-            dGI = torch.empty((B, Fr, 3 * D), device=dev, dtype=torch.float32)
-        if seq:
-            H.before_persistent_sweep()   # (DP: in-flight all-reduces finish first)
-        if xbw > 0:
-            # reverse sweep in one persistent launch, row groups per XCD, W_hh^T in VGPRs
-            work = torch.empty(xbw, device=dev, dtype=torch.uint8)
-            dOutc = dOut.contiguous()
-            _STATS['gru_xcd_bwd'] += 1
-            ev = H.roof_begin()
-            H.lib().call('srnn_gru_xcd_bwd2', H.dcode(T), B, D, Fr, H.ptr(dOutc), Fr * D, D,
-                         H.ptr(gates[l]), Fr * 4 * D, 4 * D, H.ptr(outs[l]), Fr * D, D,
-                         H.ptr(h_in[l]), H.ptr(WhhT), None, H.ptr(dGHT), None, H.ptr(dGIT),
-                         H.ptr(bsum), Fr * 3 * D, 3 * D, H.ptr(ddir[0]), H.ptr(work), xbw,
-                         st())
-            # (the dgh_{t+1} W_hh products of steps 1 .. F-1; step F-1 has none)
-            H.roof_end('gru_xcd_bwd', ev, 2.0 * B * (Fr - 1) * 3 * D * D)
-        elif seq:
-            # the whole reverse sweep in one persistent launch (W_hh^T resident in LDS)
-            work = torch.empty(64 * ((B + 31) // 32) + 1, device=dev, dtype=torch.int32)
-            dOutc = dOut.contiguous()
-            H.lib().call('srnn_gru_seq_bwd', H.dcode(T), B, D, Fr, H.ptr(dOutc), Fr * D, D,
-                         H.ptr(gates[l]), Fr * 4 * D, 4 * D, H.ptr(outs[l]), Fr * D, D,
-                         H.ptr(h_in[l]), H.ptr(WhhT), H.ptr(dGH), H.ptr(dGHT), H.ptr(dGI),
-                         Fr * 3 * D, 3 * D, H.ptr(ddir[0]), H.ptr(work), work.numel() * 4,
-                         st())
-        if seq:
-            H.after_persistent_sweep()    # (DP: gradient buckets ready before it go out now)
-        _STATS['gru_cell_bwd_steps'] += 0 if seq else Fr
-        for t in reversed(range(Fr)) if not seq else ():
-            nxt = t + 1 < Fr
-            if t > 0:
-                hp, ldhp = outs[l][:, t - 1], Fr * D
-            else:
-                hp, ldhp = h_in[l], D
-            H.lib().call('srnn_gru_cell_bwd', H.dcode(T), B, D, H.ptr(dOut[:, t]), Fr * D,
-                         H.ptr(dGHT[:, t + 1]) if nxt else None, Fr * 3 * D,
-                         H.ptr(ddir[(t + 1) % 2]) if nxt else None, H.ptr(Whh[l]),
-                         H.ptr(WhhT), H.ptr(gates[l][:, t]), Fr * 4 * D, H.ptr(hp), ldhp,
-                         H.ptr(dGH[:, t]), Fr * 3 * D,
-                         H.ptr(dGHT[:, t]) if lp else None, Fr * 3 * D,
-                         H.ptr(dGI[:, t]), Fr * 3 * D, H.ptr(ddir[t % 2]), st())
+        dGH, dGHT, dGI, dGIT, bsum, ddir0 = _gru_layer_backward(
+            T, B, D, Fr, dOut, gates[l], outs[l], h_in[l], Whh[l], WhhT)
         # dh_0 = dgh_0 . W_hh + dh_direct, as an NT product on W_hh^T (skinny ring path)
         dh_in[l] = H.gemm(dGHT[:, 0], WhhT, transB=True, M=B, N=D, K=3 * D,
-                          lda=Fr * 3 * D, ldb=3 * D, cin=ddir[0], beta=1.0)
+                          lda=Fr * 3 * D, ldb=3 * D, cin=ddir0, beta=1.0)
         # previous hidden states of every step: [h_in, out[:, :F-1]] (written by the
         # persistent forward sweep when it ran, else built here)
         hprevT = hprevs[l]

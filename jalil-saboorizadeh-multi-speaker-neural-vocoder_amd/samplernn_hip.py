@@ -74,6 +74,14 @@ _SIGS = {
     'srnn_colsum': [_I, _P, _L, _L, _I, _P, _F, _I, _P, _L, _P],
     'srnn_adam_clip': [_P, _P, _P, _P, _P, _L, _F, _F, _D, _D, _D, _D, _L, _P],
     'srnn_adam_clip_multi': [_I, _P, _P, _P, _P, _P, _P, _F, _F, _D, _D, _D, _D, _L, _P],
+    'srnn_gru_layer_plan': [_I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_SZ),
+                            ctypes.POINTER(_SZ)],
+    'srnn_gru_layer_plan_for': [_I, _I, _I, _I, _I, ctypes.POINTER(_I), ctypes.POINTER(_SZ),
+                                ctypes.POINTER(_SZ)],
+    'srnn_gru_layer_fwd': [_I, _I, _I, _I, _P, _L, _L, _P, _P, _P, _P, _P, _L, _L, _P, _L, _L, _P,
+                           _P, _SZ, _P],
+    'srnn_gru_layer_bwd': [_I, _I, _I, _I, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _P, _P, _P, _P,
+                           _P, _P, _P, _L, _L, _P, _P, _SZ, _P],
     'srnn_gru_seq_fwd': [_I, _I, _I, _I, _P, _L, _L, _P, _P, _P, _P, _P, _P, _L, _L, _P, _L, _L,
                          _P, _SZ, _P],
     'srnn_gru_seq_bwd': [_I, _I, _I, _I, _P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _P, _P, _P, _P,
@@ -333,10 +341,8 @@ def set_device_share(n):
     multi-rank rehearsal on one GPU; 1 normally).  Persistent sweeps and the generation loop
     then only take launch shapes whose grids fit the device n times over (their co-residency
     guarantee, csrc/handoff.hpp), chaining smaller launches or taking the per-step kernels
-    otherwise.  Call before the first model step (the support predicates are cached)."""
+    otherwise.  Call before the first model step."""
     lib().call('srnn_set_device_share', int(n))
-    _GRU_XCD.clear()
-    _GRU_SEQ.clear()
 
 
 class PersistentErrorWatch:
@@ -388,35 +394,41 @@ class PersistentErrorWatch:
         check_persistent_errors()       # synchronises, clears the flag and raises
 
 
-_GRU_XCD = {}
+GRU_BACKENDS = ('steps', 'seq', 'xcd')          # the C ABI's SrnnGruBackend
+
+
+def gru_layer_plan(dtype, B, D):
+    """(back end name, forward work bytes, backward work bytes) of srnn_gru_layer_fwd / _bwd
+    for (B, D) on this device: the library's choice among GRU_BACKENDS (csrc/gru_layer.hpp;
+    SRNN_GRU_XCD=0 / SRNN_GRU_SEQ=0 and set_device_share change it, so it is asked per call)."""
+    be, fb, bb = _I(0), _SZ(0), _SZ(0)
+    lib().call('srnn_gru_layer_plan', dcode(dtype), B, D, ctypes.byref(be), ctypes.byref(fb),
+               ctypes.byref(bb))
+    return GRU_BACKENDS[be.value], fb.value, bb.value
+
+
+def _gru_query(name, restype, dtype, B, D):
+    fn = getattr(lib().dll, name)
+    fn.argtypes = [_I, _I, _I]
+    fn.restype = restype
+    return fn(dcode(dtype), B, D)
 
 
 def gru_xcd_work_bytes(dtype, B, D):
-    """Work-buffer bytes of the XCD-grouped persistent GRU forward (gru_xcd.hip) for (B, D),
+    """Work-buffer bytes of the forced XCD-grouped GRU forward (srnn_gru_xcd_fwd) for (B, D),
     0 when it does not apply (SRNN_GRU_XCD=0 disables it)."""
-    if os.environ.get('SRNN_GRU_XCD', '1') == '0':
-        return 0
-    key = (dtype, B, D)
-    if key not in _GRU_XCD:
-        fn = lib().dll.srnn_gru_xcd_work_bytes
-        fn.argtypes = [_I, _I, _I]
-        fn.restype = _SZ
-        _GRU_XCD[key] = int(fn(dcode(dtype), B, D))
-    return _GRU_XCD[key]
+    return int(_gru_query('srnn_gru_xcd_work_bytes', _SZ, dtype, B, D))
 
 
 def gru_xcd_bwd_work_bytes(dtype, B, D):
-    """Work-buffer bytes of the XCD-grouped persistent GRU backward, 0 when it does not
-    apply (SRNN_GRU_XCD=0 disables it)."""
-    if os.environ.get('SRNN_GRU_XCD', '1') == '0':
-        return 0
-    key = ('bwd', dtype, B, D)
-    if key not in _GRU_XCD:
-        fn = lib().dll.srnn_gru_xcd_bwd_work_bytes
-        fn.argtypes = [_I, _I, _I]
-        fn.restype = _SZ
-        _GRU_XCD[key] = int(fn(dcode(dtype), B, D))
-    return _GRU_XCD[key]
+    """The same for the backward (srnn_gru_xcd_bwd)."""
+    return int(_gru_query('srnn_gru_xcd_bwd_work_bytes', _SZ, dtype, B, D))
+
+
+def gru_seq_supported(dtype, B, D):
+    """Whether the forced whole-sequence kernels (srnn_gru_seq_fwd / _bwd) can run (B, D)
+    here (SRNN_GRU_SEQ=0 disables them)."""
+    return bool(_gru_query('srnn_gru_seq_supported', _I, dtype, B, D))
 
 
 def gen_persistent_rows(dtype, n_seqs, dim, fs0, q_levels=256, ctrl=False):
@@ -447,23 +459,6 @@ def sample_rows(logits, noise=None, seed=0, row0=0, step=0, temperature=None, to
                                            int(step), temperature, top_k, top_p,
                                            bool(return_logp))
     return (idx, logp) if return_logp else idx
-
-
-_GRU_SEQ = {}
-
-
-def gru_seq_supported(dtype, B, D):
-    """Whether the persistent whole-sequence GRU kernel can run (B, D) here (queried once;
-    SRNN_GRU_SEQ=0 disables it)."""
-    if os.environ.get('SRNN_GRU_SEQ', '1') == '0':
-        return False
-    key = (dtype, B, D)
-    if key not in _GRU_SEQ:
-        fn = lib().dll.srnn_gru_seq_supported
-        fn.argtypes = [_I, _I, _I]
-        fn.restype = _I
-        _GRU_SEQ[key] = bool(fn(dcode(dtype), B, D))
-    return _GRU_SEQ[key]
 
 
 # ------------------------------------------------------------------ helpers
