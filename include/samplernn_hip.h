@@ -662,6 +662,102 @@ int srnn_generate6(const SrnnModel* m, int n_seqs, int n_cond, const float* cond
 int srnn_gen_state_fresh(const SrnnModel* m, int n_seqs, void* state_out, size_t state_bytes,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- generation sessions: weights, workspace and graph kept across chunks -------------------
+ * A session runs consecutive srnn_generate6 calls of one (model, n_seqs, control level, flags)
+ * without their per-call set-up: the tick weights are folded, the workspace laid out and the
+ * rows' fresh records made once, at open, and the captured generation block is replayed by every
+ * later chunk.  What a chunk computes is what the srnn_generate6 call with the same inputs,
+ * state_in = the session's records and rows = {noise_row, the records' step counts} computes, bit
+ * for bit: a session always runs on the per-row-origin path.  Replaces nothing in the reference.
+ * Device memory is the caller's: one arena of srnn_gen_session_bytes bytes, 256-byte aligned,
+ * which the session carves and which must stay allocated and untouched until close.  The
+ * SrnnModel is copied at open; the weights its pointers name must stay valid and UNCHANGED for
+ * the session's life (the folded weights are made from them once).  A session's work runs on a
+ * private stream; a session is used by one host thread at a time.                              */
+typedef struct SrnnGenSession SrnnGenSession;
+
+#define SRNN_GEN_SESSION_GRAPH      1   /* replay the generation blocks as hipGraphs          */
+#define SRNN_GEN_SESSION_PER_SAMPLE 2   /* per-sample kernels, not the persistent sample loop */
+#define SRNN_GEN_SESSION_LOGP       4   /* chunks may ask for log-probs                       */
+#define SRNN_GEN_SESSION_NOISE      8   /* every chunk brings replayed noise (no Philox)      */
+
+/* Arena bytes of a session.  Domains: n_seqs >= 1, max_frames >= 1, level in {0, 1, 2} (the
+ * sampling controls its chunks may carry: 0 none, 1 temperature / top_k / a forced prefix, 2
+ * with top_p), flags a sum of SRNN_GEN_SESSION_*.  Writes *bytes; 1 on bad arguments.          */
+int srnn_gen_session_bytes(const SrnnModel* m, int n_seqs, int max_frames, int level, int flags,
+                           size_t* bytes);
+/* Opens a session in `arena` and writes its handle to *out: validates, folds the tick weights
+ * (what every srnn_generate call does at its start) and gives every row a fresh record
+ * (srnn_gen_state_fresh's, step count 0).  Controls start at their defaults (temperature 1, top_k
+ * off, top_p 1), the Philox row of row b at row0 + b.  seed: the Philox key of every chunk.
+ * stream: work already queued there is waited for.  Synchronises before it returns.  Returns 1
+ * (nothing queued, *out = NULL) on bad arguments or an arena smaller than
+ * srnn_gen_session_bytes, 2 on a HIP error.                                                   */
+int srnn_gen_session_open(const SrnnModel* m, int n_seqs, int max_frames, int level,
+                          uint64_t seed, int row0, int flags, void* arena, size_t arena_bytes,
+                          void* stream, SrnnGenSession** out);
+
+typedef struct SrnnGenChunk {
+    int n_frames;               /* conditioning frames of this chunk, in [1, max_frames]        */
+    const float* cond;          /* device (n_seqs, n_frames, cond_dim)                          */
+    const float* row_bias;      /* device (n_seqs, D), or NULL: as in the previous chunk; the
+                                 * first chunk must give it                                    */
+    const float* temperature;   /* device (n_seqs) each, or NULL: as in the previous chunk.     */
+    const int32_t* top_k;       /*   temperature / top_k need level >= 1, top_p level 2;        */
+    const float* top_p;         /*   domains as srnn_generate4 states them                      */
+    const int64_t* prefix;      /* device (n_seqs, prefix_cols) forced samples in [0, Q), with  */
+    int prefix_cols;            /*   n_forced device (n_seqs), as srnn_generate5's n_forced; or */
+    const int32_t* n_forced;    /*   both NULL: nothing is forced in this chunk.  Level >= 1,
+                                 *   prefix_cols in [1, n_frames * L], n_frames * L < 2^23      */
+    const int32_t* noise_row;   /* HOST (n_seqs) Philox rows, every value >= 0, or NULL: as in
+                                 * the previous chunk                                          */
+    const float* noise;         /* device (n_frames * L, n_seqs, Q) Exp(1) draws: given exactly
+                                 * by the chunks of a SRNN_GEN_SESSION_NOISE session            */
+    int64_t* seq_out;           /* (n_seqs, n_frames * L) int64 sample indices, device or pinned
+                                 * host memory, or NULL                                        */
+    float* logp_out;            /* (n_frames * L, n_seqs, Q) fp32 log-probs, device or pinned
+                                 * host memory, or NULL; needs SRNN_GEN_SESSION_LOGP            */
+} SrnnGenChunk;
+
+/* Queues one chunk on the session's stream and returns without waiting for it: the inputs are
+ * copied into the session's buffers (after the work already queued on `stream`), the rows' step
+ * origins are taken on the device from their records, the blocks run from the records (the
+ * first two-period and the first one-period block of a session eagerly, the second of each
+ * captured, every later one a replay), the end state is packed into the records, and seq_out /
+ * logp_out are written.  The caller's buffers must stay valid until srnn_gen_session_sync.
+ * Returns 1, with nothing queued, where the chunk is outside the domains above, where a row's
+ * step count + n_frames * L overflows the 32-bit Philox counter, or where row_bias was never
+ * given; 2 on a HIP error, which poisons the session: this and every later call return 2 with
+ * the first error's text and launch nothing.                                                  */
+int srnn_gen_session_chunk(SrnnGenSession* s, const SrnnGenChunk* chunk, void* stream);
+/* Waits for the session's queued work; 2 (and a poisoned session) where it failed or the
+ * persistent sample loop raised its error word, as srnn_generate reports it.                   */
+int srnn_gen_session_sync(SrnnGenSession* s);
+/* Copies the rows' records (srnn_gen_state_bytes(m, n_seqs) bytes, the layout srnn_generate5
+ * reads) to `records`, device or pinned host memory, after the queued chunks; synchronises.     */
+int srnn_gen_session_state_get(SrnnGenSession* s, void* records, size_t bytes);
+/* Replaces the whole records of rows rows[0..n) (HOST array, distinct values in [0, n_seqs))
+ * by the n records at `records` (device, 8-byte aligned, bytes = n * srnn_gen_state_bytes(m, 1),
+ * else return code 1); their step counts become the rows'.  Every header is checked on the host
+ * against the session's layout before anything is written (return code 1 and srnn_generate5's
+ * message).  Waits for the work queued on `stream` and synchronises the session's.              */
+int srnn_gen_session_state_set_rows(SrnnGenSession* s, const int32_t* rows, int n,
+                                    const void* records, size_t bytes, void* stream);
+
+typedef struct SrnnGenSessionStats {
+    int64_t prepares;           /* times the tick weights were folded (1: at open)              */
+    int64_t graphs_captured;    /* blocks captured and instantiated (at most 2)                 */
+    int64_t graph_launches;     /* blocks run as a graph launch                                 */
+    int64_t eager_blocks;       /* blocks run as plain launches                                 */
+    int64_t chunks;             /* chunks queued                                                */
+    int64_t steps_min, steps_max;   /* the host mirror of the rows' step counts                 */
+} SrnnGenSessionStats;
+/* Diagnostic counters of a session (the idiom of srnn_blaslt_calls): host values, no HIP call. */
+int srnn_gen_session_stats(const SrnnGenSession* s, SrnnGenSessionStats* stats);
+/* Drains the session's stream, then releases its stream, graphs and host memory (the arena is
+ * the caller's again), on every path; NULL is allowed.  2 where the drain reports a HIP error. */
+int srnn_gen_session_close(SrnnGenSession* s);
+
 #ifdef __cplusplus
 }
 #endif

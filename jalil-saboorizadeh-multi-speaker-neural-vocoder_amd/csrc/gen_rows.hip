@@ -59,6 +59,37 @@ int srnn_sample_origin_impl(const float* z, int64_t ldz, int B, const float* noi
     return 0;
 }
 
+// A generation session's rows (generate.hip): the Philox step origin of row b is the step count
+// of its state record (the int64 at word `word` of a record of rw words; the host has checked
+// that it fits 32 bits), taken on the device so that a chunk needs no host round trip.
+__global__ __launch_bounds__(256) void gen_rows_step0_kernel(const uint32_t* __restrict__ records,
+                                                             int64_t rw, int word, int B,
+                                                             uint32_t* __restrict__ step0) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b < B) step0[b] = records[(int64_t)b * rw + word];
+}
+
+int gen_rows_step0_launch(const void* records, int64_t rw, int word, int B, uint32_t* step0,
+                          hipStream_t s) {
+    hipLaunchKernelGGL(gen_rows_step0_kernel, dim3(cdiv(B, 256)), dim3(256), 0, s,
+                       (const uint32_t*)records, rw, word, B, step0);
+    SRNN_LAUNCH_CHECK();
+    return 0;
+}
+
+// The persistent loop's error word of a chunk (zeroed at every chunk's start) into the session's
+// sticky one: the first error stays.  `err` null (per-sample kernels): nothing to take.
+__global__ void gen_rows_err_kernel(const int* __restrict__ err, int* __restrict__ sticky) {
+    if (*sticky == 0 && *err != 0) *sticky = *err;
+}
+
+int gen_rows_err_launch(const int* err, int* sticky, hipStream_t s) {
+    if (!err) return 0;
+    hipLaunchKernelGGL(gen_rows_err_kernel, dim3(1), dim3(1), 0, s, err, sticky);
+    SRNN_LAUNCH_CHECK();
+    return 0;
+}
+
 // log q of the draws of nsteps generation steps, one wave per (step, row), as gen_noise_kernel
 __global__ __launch_bounds__(256) void gen_noise_origin_kernel(
     const float* __restrict__ noise, uint64_t seed, int row0, const int* __restrict__ base,

@@ -33,6 +33,9 @@ int srnn_sample_origin_impl(const float* z, int64_t ldz, int B, const float* noi
                             const float* temperature, const int* top_k, const float* top_p,
                             uint32_t step0, const int* n_forced, const int* noise_row,
                             const uint32_t* row_step0, hipStream_t s);
+int gen_rows_step0_launch(const void* records, int64_t rw, int word, int B, uint32_t* step0,
+                          hipStream_t s);
+int gen_rows_err_launch(const int* err, int* sticky, hipStream_t s);
 
 // Fused tier input (build_input + input projection of one tier tick), one row per block:
 //   a[s] = 2*deq(seq[b, i - nfs + s]) (s < nfs) | cond[b, i/L - 1, s - nfs]   (rounded to T,
@@ -376,10 +379,11 @@ __global__ __launch_bounds__(256) void gen_state_unpack_kernel(
 }
 
 // The reverse; st_in (or null: a fresh start) supplies the rows' earlier step counts and may be
-// st_out itself: only the thread that writes a row's count reads it.
+// st_out itself: only the thread that writes a row's count reads it.  The rows' last L samples
+// are seq columns [hist, hist + L) (a call: its last; a session's chunk: the chunk's last).
 __global__ __launch_bounds__(256) void gen_state_pack_kernel(
     uint32_t* __restrict__ st_out, const uint32_t* st_in, int64_t rw, GenStateMap mp,
-    const int64_t* __restrict__ seq, int64_t ldseq, int64_t T) {
+    const int64_t* __restrict__ seq, int64_t ldseq, int64_t hist, int64_t T) {
     int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int b = blockIdx.y;
     if (w >= rw) return;
@@ -399,7 +403,7 @@ __global__ __launch_bounds__(256) void gen_state_pack_kernel(
     uint32_t v = 0u;
     if (w < mp.L) {
         // (no seq: the q_zero history of a stream that has done no step)
-        v = seq ? (uint32_t)seq[(int64_t)b * ldseq + (ldseq - mp.L) + w] : mp.q_zero;
+        v = seq ? (uint32_t)seq[(int64_t)b * ldseq + hist + w] : mp.q_zero;
     } else if (w - mp.L < (int64_t)mp.n_h * D) {
         const int64_t e = w - mp.L;
         const int j = (int)(e / D), u = (int)(e - (int64_t)j * D);
@@ -912,7 +916,7 @@ int64_t gen_state_row_words(const SrnnModel* m, const GenSwitches& sw) {
 
 // ---- the phases of a call (gen_run) ------------------------------------------------------
 // gen_validate and gen_prepare depend on (model, n_seqs, control level, switches) and the
-// workspace only -- what a streaming session would keep between chunks; gen_start, gen_blocks
+// workspace only -- what a session (below) keeps between its chunks; gen_start, gen_blocks
 // and gen_finish are this call's.
 
 // The rows' own Philox origins, read back (the only HIP call of the validation, and it queues
@@ -946,9 +950,8 @@ int gen_validate_rows(Ctx& c) {
     return 0;
 }
 
-// Checks the request and lays the call out (plan, workspace, state record).  No HIP work is
-// queued before the last check has passed.
-int gen_validate(Ctx& c) {
+// Checks the request and lays the call out (plan, workspace, state record): host work only.
+int gen_layout(Ctx& c) {
     const GenRequest& r = c.rq;
     const SrnnModel* m = r.m;
     SRNN_REQUIRE(r.row0 >= 0, "generate: negative row offset");
@@ -998,6 +1001,12 @@ int gen_validate(Ctx& c) {
                              (c.b.fold ? 1u : 0u) | (c.b.fold_top ? 2u : 0u), 0u};
     memcpy(mp.hdr, hdr, sizeof(hdr));
     mp.q_zero = (uint32_t)(m->q_levels / 2);
+    return 0;
+}
+
+// No HIP work is queued before the last check has passed.
+int gen_validate(Ctx& c) {
+    RET(gen_layout(c));
     return gen_validate_rows(c);
 }
 
@@ -1118,65 +1127,105 @@ int gen_init_state(Ctx& c) {
     return 0;
 }
 
-// This call's start: the block base and the hand-off block, the fresh (or carried) recurrent
-// state, and what follows from it and from row_bias.
-int gen_start(Ctx& c) {
-    const GenRequest& r = c.rq;
-    const SrnnModel* m = r.m;
-    const int D = m->dim, B = r.n_seqs, dt = m->dtype;
-    const bool lp = dt != SRNN_F32;
-    hipStream_t s = c.s;
-    if (r.state_in) {
-        // every record's header must be one of this call's layout: checked on the host before
-        // anything of this call's own is launched
-        std::vector<uint32_t> hd((size_t)B * 8);
-        if (hipMemcpy2DAsync(hd.data(), 32, r.state_in, (size_t)c.rw * 4, 32, B,
-                             hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) {
-            srnn_set_error("generate: reading the state headers: %s",
-                           hipGetErrorString(hipGetLastError()));
-            return 2;
-        }
-        const uint32_t* w = c.mp.hdr;
-        for (int b = 0; b < B; ++b) {
-            const uint32_t* h = hd.data() + (size_t)b * 8;
-            SRNN_REQUIRE(memcmp(h, w, 32) == 0,
-                         "generate: state row %d has layout (tag %08x, dtype %u, tiers %u, rnn %u, "
-                         "dim %u, L %u, fold %u), this call needs (tag %08x, dtype %u, tiers %u, "
-                         "rnn %u, dim %u, L %u, fold %u)", b, h[0], h[1], h[2], h[3], h[4], h[5],
-                         h[6], w[0], w[1], w[2], w[3], w[4], w[5], w[6]);
-        }
+// The headers (8 words each, read from the device onto stream s) of n records of row stride
+// c.rw words must be of this call's layout: checked on the host before anything that uses the
+// records is launched.
+int gen_check_headers(Ctx& c, const void* records, int n, hipStream_t s) {
+    std::vector<uint32_t> hd((size_t)n * 8);
+    if (hipMemcpy2DAsync(hd.data(), 32, records, (size_t)c.rw * 4, 32, n, hipMemcpyDeviceToHost,
+                         s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess) {
+        srnn_set_error("generate: reading the state headers: %s",
+                       hipGetErrorString(hipGetLastError()));
+        return 2;
     }
+    const uint32_t* w = c.mp.hdr;
+    for (int b = 0; b < n; ++b) {
+        const uint32_t* h = hd.data() + (size_t)b * 8;
+        SRNN_REQUIRE(memcmp(h, w, 32) == 0,
+                     "generate: state row %d has layout (tag %08x, dtype %u, tiers %u, rnn %u, "
+                     "dim %u, L %u, fold %u), this call needs (tag %08x, dtype %u, tiers %u, "
+                     "rnn %u, dim %u, L %u, fold %u)", b, h[0], h[1], h[2], h[3], h[4], h[5],
+                     h[6], w[0], w[1], w[2], w[3], w[4], w[5], w[6]);
+    }
+    return 0;
+}
+
+// The block base (sample L) and the zeroed hand-off block of a call.
+int gen_reset(Ctx& c) {
+    hipStream_t s = c.s;
     SRNN_CHECK_HIP(hipMemsetAsync(c.b.base, 0, 64, s));
     if (c.pl) SRNN_CHECK_HIP(hipMemsetAsync(c.b.gerr, 0, c.b.gm_bytes, s));
     // (from c.L: the context outlives the drain)
     SRNN_CHECK_HIP(hipMemcpyAsync(c.b.base, &c.L, sizeof(int), hipMemcpyHostToDevice, s));
+    return 0;
+}
+
+// With the folded top tick P1 = bf16(row_bias) . W_ih1^T + b_ih1 (else nothing: the top tier's
+// input launch adds row_bias itself).
+int gen_top_bias(Ctx& c) {
+    if (!c.b.fold_top) return 0;
+    const GenRequest& r = c.rq;
+    const SrnnModel* m = r.m;
+    const int D = m->dim, B = r.n_seqs, dt = m->dtype;
+    const SrnnTier& t1 = m->tier[1];
+    RET(gen_typed_launch(dt, [&](auto z) {
+        using T = decltype(z);
+        hipLaunchKernelGGL((copy_cast_kernel<T>), dim3(cdiv(B * D, 256)), dim3(256), 0, c.s,
+                           r.row_bias, (T*)c.b.x[1], B * D);
+    }));
+    return linear_fwd(dt, SRNN_F32, B, 3 * D, D, c.b.x[1], D, t1.w_ih[0], D, t1.b_ih[0], c.b.p1,
+                      3 * D, 0, c.s);
+}
+
+// The carried state `records` into the workspace: buffer [0] of every h (and its T copy), the
+// folded ticks' gh rows and the sample history seq[:, 0:L).
+int gen_unpack(Ctx& c, const void* records) {
+    const GenRequest& r = c.rq;
+    const SrnnModel* m = r.m;
+    const bool lp = m->dtype != SRNN_F32;
+    GenStateMap mp = c.mp;
+    for (int k = 0; k < m->n_tiers; ++k)
+        for (int l = 0; l < m->n_rnn; ++l) {
+            mp.h[k * m->n_rnn + l] = c.b.h[k][l][0];
+            mp.hlp[k * m->n_rnn + l] = lp ? c.b.hlp[k][l][0] : nullptr;
+        }
+    return gen_typed_launch(m->dtype, [&](auto z) {
+        using T = decltype(z);
+        hipLaunchKernelGGL((gen_state_unpack_kernel<T>), dim3(cdiv(c.rw, 256), r.n_seqs),
+                           dim3(256), 0, c.s, (const uint32_t*)records, c.rw, mp, r.seq, c.ldseq);
+    });
+}
+
+// This call's start: the block base and the hand-off block, the fresh (or carried) recurrent
+// state, and what follows from it and from row_bias.
+int gen_start(Ctx& c) {
+    const GenRequest& r = c.rq;
+    // every record's header must be one of this call's layout: checked on the host before
+    // anything of this call's own is launched
+    if (r.state_in) RET(gen_check_headers(c, r.state_in, r.n_seqs, c.s));
+    RET(gen_reset(c));
     RET(gen_init_state(c));
-    if (c.b.fold_top) {
-        // with the folded top tick P1 = bf16(row_bias) . W_ih1^T + b_ih1
-        const SrnnTier& t1 = m->tier[1];
-        RET(gen_typed_launch(dt, [&](auto z) {
-            using T = decltype(z);
-            hipLaunchKernelGGL((copy_cast_kernel<T>), dim3(cdiv(B * D, 256)), dim3(256), 0, s,
-                               r.row_bias, (T*)c.b.x[1], B * D);
-        }));
-        RET(linear_fwd(dt, SRNN_F32, B, 3 * D, D, c.b.x[1], D, t1.w_ih[0], D, t1.b_ih[0], c.b.p1,
-                       3 * D, 0, s));
+    RET(gen_top_bias(c));
+    // the carried state replaces the fresh start's
+    if (r.state_in) RET(gen_unpack(c, r.state_in));
+    return 0;
+}
+
+// One block of `periods` periods captured from the call's stream and instantiated (an earlier
+// block has run eagerly: it raised the per-kernel attributes, outside any capture).
+int gen_capture(Ctx& c, int periods, hipGraph_t* graph, hipGraphExec_t* exec) {
+    if (hipStreamBeginCapture(c.s, hipStreamCaptureModeThreadLocal) != hipSuccess) {
+        srnn_set_error("generate: begin capture failed");
+        return 2;
     }
-    if (r.state_in) {
-        // the carried state replaces the fresh start's: buffer [0] of every h (and its T
-        // copy), the folded ticks' gh rows and the sample history seq[:, 0:L)
-        GenStateMap mp = c.mp;
-        for (int k = 0; k < m->n_tiers; ++k)
-            for (int l = 0; l < m->n_rnn; ++l) {
-                mp.h[k * m->n_rnn + l] = c.b.h[k][l][0];
-                mp.hlp[k * m->n_rnn + l] = lp ? c.b.hlp[k][l][0] : nullptr;
-            }
-        RET(gen_typed_launch(dt, [&](auto z) {
-            using T = decltype(z);
-            hipLaunchKernelGGL((gen_state_unpack_kernel<T>), dim3(cdiv(c.rw, 256), B), dim3(256),
-                               0, s, (const uint32_t*)r.state_in, c.rw, mp, r.seq, c.ldseq);
-        }));
+    // (the capture is ended after a failed block too: the stream must leave capture mode)
+    const int rc = run_block(c, periods);
+    const hipError_t ce = hipStreamEndCapture(c.s, graph);
+    RET(rc);
+    if (ce != hipSuccess || hipGraphInstantiate(exec, *graph, nullptr, nullptr, 0) != hipSuccess) {
+        srnn_set_error("generate: graph capture/instantiate failed");
+        return 2;
     }
     return 0;
 }
@@ -1192,19 +1241,7 @@ int gen_blocks(Ctx& c) {
         done = 1;
     }
     if ((c.rq.flags & 1) && nblocks > 1) {
-        if (hipStreamBeginCapture(c.s, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-            srnn_set_error("generate: begin capture failed");
-            return 2;
-        }
-        // (the capture is ended after a failed block too: the stream must leave capture mode)
-        const int rc = run_block(c, 2);
-        const hipError_t ce = hipStreamEndCapture(c.s, &c.gs.graph);
-        RET(rc);
-        if (ce != hipSuccess ||
-            hipGraphInstantiate(&c.gs.exec, c.gs.graph, nullptr, nullptr, 0) != hipSuccess) {
-            srnn_set_error("generate: graph capture/instantiate failed");
-            return 2;
-        }
+        RET(gen_capture(c, 2, &c.gs.graph, &c.gs.exec));
         for (; done < nblocks; ++done)
             if (hipGraphLaunch(c.gs.exec, c.s) != hipSuccess) {
                 srnn_set_error("generate: graph launch failed");
@@ -1216,31 +1253,38 @@ int gen_blocks(Ctx& c) {
     return 0;
 }
 
+// The records `out` of the state after T more steps than `in` counts (null: a fresh start), the
+// rows' last L samples being seq columns [hist, hist + L).  `odd`: the steps ended in a
+// one-period block.
+int gen_pack(Ctx& c, void* out, const void* in, bool odd, const int64_t* seq, int64_t hist,
+             int64_t T) {
+    const SrnnModel* m = c.rq.m;
+    // tick parity restarts at 0 in every block and the two-period blocks tick every tier
+    // an even number of times, so only a trailing one-period block moves a tier's live h:
+    // to buffer [1] where the tier ticks an odd number of times per period (the top tier
+    // always does)
+    GenStateMap mp = c.mp;
+    for (int k = 0; k < m->n_tiers; ++k) {
+        const int live = odd ? (c.L / m->tier[k].n_frame_samples) & 1 : 0;
+        for (int l = 0; l < m->n_rnn; ++l) mp.h[k * m->n_rnn + l] = c.b.h[k][l][live];
+    }
+    hipLaunchKernelGGL(gen_state_pack_kernel, dim3(cdiv(c.rw, 256), c.rq.n_seqs), dim3(256), 0,
+                       c.s, (uint32_t*)out, (const uint32_t*)in, c.rw, mp, seq, c.ldseq, hist, T);
+    if (hipGetLastError() != hipSuccess) {
+        srnn_set_error("generate: state pack launch");
+        return 2;
+    }
+    return 0;
+}
+
 // Runs whatever the earlier phases returned (rc): packs the end state of a call that got
 // through, drains the private stream before its resources go (generation is one long call),
 // and reads the persistent loop's error word.
 int gen_finish(Ctx& c, int rc) {
     const GenRequest& r = c.rq;
-    const SrnnModel* m = r.m;
-    if (!rc && r.state_out) {
-        // tick parity restarts at 0 in every block and the two-period blocks tick every tier
-        // an even number of times, so only a trailing one-period block moves a tier's live h:
-        // to buffer [1] where the tier ticks an odd number of times per period (the top tier
-        // always does)
-        GenStateMap mp = c.mp;
-        for (int k = 0; k < m->n_tiers; ++k) {
-            const int live =
-                (!c.fresh && r.n_cond % 2) ? (c.L / m->tier[k].n_frame_samples) & 1 : 0;
-            for (int l = 0; l < m->n_rnn; ++l) mp.h[k * m->n_rnn + l] = c.b.h[k][l][live];
-        }
-        hipLaunchKernelGGL(gen_state_pack_kernel, dim3(cdiv(c.rw, 256), r.n_seqs), dim3(256), 0,
-                           c.s, (uint32_t*)r.state_out, (const uint32_t*)r.state_in, c.rw, mp,
-                           c.fresh ? nullptr : r.seq, c.ldseq, c.T);
-        if (hipGetLastError() != hipSuccess) {
-            srnn_set_error("generate: state pack launch");
-            rc = 2;
-        }
-    }
+    if (!rc && r.state_out)
+        rc = gen_pack(c, r.state_out, r.state_in, !c.fresh && r.n_cond % 2,
+                      c.fresh ? nullptr : r.seq, c.ldseq - c.L, c.T);
     if (hipStreamSynchronize(c.s) != hipSuccess && !rc) {
         srnn_set_error("generate: %s", hipGetErrorString(hipGetLastError()));
         rc = 2;
@@ -1281,7 +1325,457 @@ int gen_fresh(const GenRequest& rq) {
     return gen_finish(c, rc);
 }
 
+// ---- sessions (srnn_gen_session_*) ---------------------------------------------------------
+// A session is a Ctx that lives on: gen_layout and gen_prepare run once, at open, over a request
+// whose every pointer names a session-owned buffer at a fixed address (the captured launches bake
+// them in), and a chunk is the per-call phases -- gen_reset, gen_unpack, the blocks, gen_pack --
+// from and to the session's own records.  The rows' Philox origins are device arrays
+// (SrnnGenRows' path), so a captured block serves every chunk.
+
+// the session's own arrays, carved from the arena ahead of the call workspace
+struct SessBufs {
+    int64_t* seq;            // (B, L (F + 1))
+    float* cond;             // (B, F, C)
+    float* row_bias;         // (B, D)
+    float* temperature;      // (B) each; level >= 1
+    int* top_k;
+    int* n_forced;
+    float* top_p;            // level 2
+    int* noise_row;
+    uint32_t* step0;
+    float* logp;             // (F L, B, Q), SRNN_GEN_SESSION_LOGP
+    float* noise;            // (F L, B, Q), SRNN_GEN_SESSION_NOISE
+    uint32_t* records;       // (B, rw)
+    int* sticky;             // the first error word a chunk's persistent loop raised
+    char* ws;                // the call workspace (carve)
+    size_t ws_bytes;
+};
+
+// What (model, n_seqs, level, flags) determine of a session's layout, checked first: the arena's
+// size and, given the arena, its carving.
+int session_carve(const SrnnModel* m, int B, int F, int level, int flags, const GenSwitches& sw,
+                  char* arena, SessBufs* sb, size_t* bytes) {
+    SRNN_REQUIRE(m && B > 0 && F > 0 && level >= 0 && level <= 2 && !(flags & ~15),
+                 "gen_session: bad args");
+    SRNN_REQUIRE(m->n_tiers >= 1 && m->n_tiers <= SRNN_MAX_TIERS, "generate: n_tiers");
+    SRNN_REQUIRE(m->n_rnn >= 1 && m->n_rnn <= SRNN_MAX_RNN, "generate: n_rnn");
+    SRNN_REQUIRE(m->q_levels == 256, "generate: q_levels must be 256");
+    SRNN_REQUIRE(m->dim > 0 && m->dim % 16 == 0, "generate: dim must be a multiple of 16");
+    const int64_t L = m->tier[m->n_tiers - 1].n_frame_samples;
+    SRNN_REQUIRE(L > 0 && m->cond_dim >= 0 && (int64_t)F * L < (1ll << 31) - L,
+                 "gen_session: max_frames %d x lookback %lld", F, (long long)L);
+    GenMlpPlan pl;
+    plan_for(m, B, level, &pl, sw);
+    if (flags & SRNN_GEN_SESSION_PER_SAMPLE) pl.ok = 0;
+    Bufs b;
+    const size_t Bz = (size_t)B, steps = (size_t)F * L;
+    size_t off = 0;
+    auto take = [&](size_t n) -> char* {
+        char* p = arena ? arena + off : nullptr;
+        off += al(n);
+        return p;
+    };
+    sb->seq = (int64_t*)take(Bz * (steps + L) * 8);
+    sb->cond = (float*)take(Bz * F * (m->cond_dim > 0 ? m->cond_dim : 1) * 4);
+    sb->row_bias = (float*)take(Bz * m->dim * 4);
+    sb->temperature = level >= 1 ? (float*)take(Bz * 4) : nullptr;
+    sb->top_k = level >= 1 ? (int*)take(Bz * 4) : nullptr;
+    sb->n_forced = level >= 1 ? (int*)take(Bz * 4) : nullptr;
+    sb->top_p = level >= 2 ? (float*)take(Bz * 4) : nullptr;
+    sb->noise_row = (int*)take(Bz * 4);
+    sb->step0 = (uint32_t*)take(Bz * 4);
+    sb->logp = (flags & SRNN_GEN_SESSION_LOGP) ? (float*)take(steps * Bz * 256 * 4) : nullptr;
+    sb->noise = (flags & SRNN_GEN_SESSION_NOISE) ? (float*)take(steps * Bz * 256 * 4) : nullptr;
+    sb->records = (uint32_t*)take((size_t)gen_state_row_words(m, sw) * 4 * Bz);
+    sb->sticky = (int*)take(64);
+    sb->ws_bytes = carve(m, B, nullptr, &b, &pl, sw);
+    sb->ws = take(sb->ws_bytes);
+    *bytes = off;
+    return 0;
+}
+
+struct Session {
+    SrnnModel model;         // the caller's, copied: rq.m
+    GenRequest rq;           // over the session's own buffers; n_cond = max_frames (the strides)
+    Ctx c;
+    SessBufs sb{};
+    const int max_frames, level, flags;
+    hipGraph_t graph[2] = {nullptr, nullptr};      // [periods - 1]: the one- and the two-period
+    hipGraphExec_t exec[2] = {nullptr, nullptr};   // block
+    bool eager_done[2] = {false, false};
+    volatile int* host_err = nullptr;              // pinned: the sticky error word, per chunk;
+                                                   // from word 16 on, a staging row of B ints
+    std::vector<int64_t> steps;                    // host mirror of the rows' step counts
+    bool have_bias = false, forced_live = false, poisoned = false;
+    bool staged = false;                           // the pinned noise_row row is in flight
+    char error[512] = {0};                         // the text of the error that poisoned it
+    SrnnGenSessionStats st{};
+    Session(const SrnnModel& m, int n_seqs, int F, int lv, uint64_t seed, int row0, int fl,
+            hipStream_t user)
+        : model(m),
+          rq{&model, n_seqs, F, nullptr, nullptr, nullptr, seed, row0, nullptr, nullptr, nullptr,
+             0, fl & 3, user},
+          c{rq, GenSwitches::read()}, max_frames(F), level(lv), flags(fl),
+          steps((size_t)n_seqs, 0) {}
+    // (a session never keeps starting work on a device after a fault)
+    int poison() {
+        if (!poisoned) snprintf(error, sizeof(error), "%s", srnn_last_error());
+        poisoned = true;
+        srnn_set_error("%s", error);
+        return 2;
+    }
+    int poison_err_word() {
+        const int e = *host_err;
+        srnn_set_error(e == 2 ? "generate: persistent sample loop's workgroups were not all "
+                                "resident within 30 s (another process holds the CUs?)"
+                              : "generate: persistent sample loop lost a hand-off (spin limit)");
+        return poison();
+    }
+    int refused() {
+        srnn_set_error("%s", error);
+        return 2;
+    }
+};
+
+int session_open(Session& se, char* arena, size_t arena_bytes) {
+    Ctx& c = se.c;
+    GenRequest& r = se.rq;
+    const SrnnModel* m = &se.model;
+    const size_t B = (size_t)r.n_seqs;
+    size_t need = 0;
+    RET(session_carve(m, r.n_seqs, se.max_frames, se.level, se.flags, c.sw, arena, &se.sb, &need));
+    SRNN_REQUIRE(arena_bytes >= need, "gen_session: arena %zu < %zu", arena_bytes, need);
+    const SessBufs& sb = se.sb;
+    r.cond = sb.cond;
+    r.row_bias = sb.row_bias;
+    r.noise = sb.noise;
+    r.seq = sb.seq;
+    r.logp = sb.logp;
+    r.workspace = sb.ws;
+    r.workspace_bytes = sb.ws_bytes;
+    r.temperature = sb.temperature;
+    r.top_k = sb.top_k;
+    r.top_p = sb.top_p;
+    r.n_forced = sb.n_forced;
+    r.noise_row = sb.noise_row;
+    r.row_step0 = sb.step0;
+    RET(gen_layout(c));
+    SRNN_REQUIRE(r.level() == se.level, "gen_session: level");
+    RET(c.gs.open(r.stream));
+    c.s = c.gs.s;
+    hipStream_t s = c.s;
+    SRNN_CHECK_HIP(hipHostMalloc((void**)&se.host_err, 64 + B * 4, hipHostMallocDefault));
+    *se.host_err = 0;
+    // the buffers a chunk may leave as they are: controls at their defaults, Philox rows
+    // row0 + b, nothing forced, a defined history
+    std::vector<float> ones(B, 1.0f);
+    std::vector<int> nrow(B);
+    for (size_t b = 0; b < B; ++b) nrow[b] = r.row0 + (int)b;
+    SRNN_CHECK_HIP(hipMemsetAsync(arena, 0, (size_t)(sb.ws - arena), s));
+    for (float* p : {sb.temperature, sb.top_p})
+        if (p) SRNN_CHECK_HIP(hipMemcpyAsync(p, ones.data(), B * 4, hipMemcpyHostToDevice, s));
+    SRNN_CHECK_HIP(hipMemcpyAsync(sb.noise_row, nrow.data(), B * 4, hipMemcpyHostToDevice, s));
+    RET(gen_prepare(c));                         // (synchronises: the staging vectors may go)
+    se.st.prepares++;
+    // every row starts from a fresh record (gen_fresh's)
+    RET(gen_init_state(c));
+    RET(gen_pack(c, sb.records, nullptr, false, nullptr, 0, 0));
+    SRNN_CHECK_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
+// Everything a chunk is refused for, before anything is queued.
+int session_check(const Session& se, const SrnnGenChunk& ck) {
+    const GenRequest& r = se.rq;
+    SRNN_REQUIRE(ck.n_frames >= 1 && ck.n_frames <= se.max_frames,
+                 "gen_session: a chunk of %d frames, the session was opened for 1..%d",
+                 ck.n_frames, se.max_frames);
+    const int64_t T = (int64_t)ck.n_frames * se.c.L;
+    SRNN_REQUIRE(ck.cond, "gen_session: no cond");
+    SRNN_REQUIRE(ck.row_bias || se.have_bias, "gen_session: the first chunk must give row_bias");
+    SRNN_REQUIRE(sample_ctrl_level(ck.temperature, ck.top_k, ck.top_p) <= se.level,
+                 "gen_session: a sampling control above the session's level %d", se.level);
+    SRNN_REQUIRE(!ck.prefix == !ck.n_forced, "gen_session: prefix and n_forced go together");
+    if (ck.prefix) {
+        SRNN_REQUIRE(se.level >= 1, "gen_session: a forced prefix needs a session of level >= 1");
+        SRNN_REQUIRE(ck.prefix_cols >= 1 && ck.prefix_cols <= T,
+                     "gen_session: prefix of %d columns for %lld steps", ck.prefix_cols,
+                     (long long)T);
+        SRNN_REQUIRE(T < (1 << 23), "generate: a forced prefix needs fewer than 2^23 "
+                     "steps per call (%lld)", (long long)T);
+    }
+    SRNN_REQUIRE(!ck.noise == !(se.flags & SRNN_GEN_SESSION_NOISE),
+                 "gen_session: replayed noise is given by exactly the chunks of a session opened "
+                 "for it");
+    SRNN_REQUIRE(!ck.logp_out || (se.flags & SRNN_GEN_SESSION_LOGP),
+                 "gen_session: log-probs need a session opened for them");
+    if (ck.noise_row)
+        for (int b = 0; b < r.n_seqs; ++b)
+            SRNN_REQUIRE(ck.noise_row[b] >= 0, "generate: noise_row[%zu] = %d is negative",
+                         (size_t)b, ck.noise_row[b]);
+    if (!(se.flags & SRNN_GEN_SESSION_NOISE))
+        for (int b = 0; b < r.n_seqs; ++b)
+            SRNN_REQUIRE((uint64_t)se.steps[b] + (uint64_t)T <= 0xFFFFFFFFull,
+                         "generate: row %zu: step0 %llu + %lld steps overflow the 32-bit Philox "
+                         "step counter", (size_t)b, (unsigned long long)se.steps[b], (long long)T);
+    return 0;
+}
+
+// One block: the first of its length eagerly (it raises kernel attributes), the second captured
+// and launched, every later one -- of this chunk and of all that follow -- a replay.
+int session_block(Session& se, int periods) {
+    Ctx& c = se.c;
+    const int k = periods - 1;
+    if (!(se.flags & SRNN_GEN_SESSION_GRAPH) || !se.eager_done[k]) {
+        RET(run_block(c, periods));
+        se.eager_done[k] = true;
+        se.st.eager_blocks++;
+        return 0;
+    }
+    if (!se.exec[k]) {
+        RET(gen_capture(c, periods, &se.graph[k], &se.exec[k]));
+        se.st.graphs_captured++;
+    }
+    if (hipGraphLaunch(se.exec[k], c.s) != hipSuccess) {
+        srnn_set_error("generate: graph launch failed");
+        return 2;
+    }
+    se.st.graph_launches++;
+    return 0;
+}
+
+// Queues a checked chunk; every step is ordered on the session's stream.
+int session_queue(Session& se, const SrnnGenChunk& ck, hipStream_t user) {
+    Ctx& c = se.c;
+    const GenRequest& r = se.rq;
+    const SessBufs& sb = se.sb;
+    const SrnnModel* m = r.m;
+    const size_t B = (size_t)r.n_seqs, n = (size_t)ck.n_frames, L = (size_t)c.L;
+    const size_t T = n * L;
+    hipStream_t s = c.s;
+    const hipMemcpyKind d2d = hipMemcpyDeviceToDevice;
+    SRNN_CHECK_HIP(hipEventRecord(c.gs.ev, user));
+    SRNN_CHECK_HIP(hipStreamWaitEvent(s, c.gs.ev, 0));
+    if (m->cond_dim > 0) {
+        const size_t fb = (size_t)m->cond_dim * 4;
+        SRNN_CHECK_HIP(hipMemcpy2DAsync(sb.cond, (size_t)se.max_frames * fb, ck.cond, n * fb,
+                                        n * fb, B, d2d, s));
+    }
+    if (ck.row_bias) {
+        SRNN_CHECK_HIP(hipMemcpyAsync(sb.row_bias, ck.row_bias, B * m->dim * 4, d2d, s));
+        RET(gen_top_bias(c));
+        se.have_bias = true;
+    }
+    if (ck.temperature)
+        SRNN_CHECK_HIP(hipMemcpyAsync(sb.temperature, ck.temperature, B * 4, d2d, s));
+    if (ck.top_k) SRNN_CHECK_HIP(hipMemcpyAsync(sb.top_k, ck.top_k, B * 4, d2d, s));
+    if (ck.top_p) SRNN_CHECK_HIP(hipMemcpyAsync(sb.top_p, ck.top_p, B * 4, d2d, s));
+    if (ck.prefix) {
+        const size_t pb = (size_t)ck.prefix_cols * 8;
+        SRNN_CHECK_HIP(hipMemcpy2DAsync(sb.seq + L, (size_t)c.ldseq * 8, ck.prefix, pb, pb, B,
+                                        d2d, s));
+        SRNN_CHECK_HIP(hipMemcpyAsync(sb.n_forced, ck.n_forced, B * 4, d2d, s));
+        se.forced_live = true;
+    } else if (se.forced_live) {
+        SRNN_CHECK_HIP(hipMemsetAsync(sb.n_forced, 0, B * 4, s));
+        se.forced_live = false;
+    }
+    if (ck.noise) SRNN_CHECK_HIP(hipMemcpyAsync(sb.noise, ck.noise, T * B * 256 * 4, d2d, s));
+    if (ck.noise_row) {
+        // through the pinned staging row (a copy from pageable memory may wait for the stream);
+        // one still in flight is waited for, whatever else that costs
+        if (se.staged) SRNN_CHECK_HIP(hipStreamSynchronize(s));
+        int* stage = (int*)se.host_err + 16;
+        memcpy(stage, ck.noise_row, B * 4);
+        SRNN_CHECK_HIP(hipMemcpyAsync(sb.noise_row, stage, B * 4, hipMemcpyHostToDevice, s));
+        se.staged = true;
+    }
+    // the per-chunk part of gen_start (gen_reset with the base set from the device side: no
+    // host memory is read), from the session's own records
+    SRNN_CHECK_HIP(hipMemsetAsync(c.b.base, 0, 64, s));
+    if (c.pl) SRNN_CHECK_HIP(hipMemsetAsync(c.b.gerr, 0, c.b.gm_bytes, s));
+    SRNN_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)c.b.base, c.L, 1, s));
+    RET(gen_rows_step0_launch(sb.records, c.rw, 8, r.n_seqs, sb.step0, s));
+    RET(gen_unpack(c, sb.records));
+    for (size_t k = 0; k < n / 2; ++k) RET(session_block(se, 2));
+    if (n % 2) RET(session_block(se, 1));
+    RET(gen_pack(c, sb.records, sb.records, n % 2 != 0, sb.seq, (int64_t)T, (int64_t)T));
+    if (ck.seq_out)
+        SRNN_CHECK_HIP(hipMemcpy2DAsync(ck.seq_out, T * 8, sb.seq + L, (size_t)c.ldseq * 8, T * 8,
+                                        B, hipMemcpyDefault, s));
+    if (ck.logp_out)
+        SRNN_CHECK_HIP(hipMemcpyAsync(ck.logp_out, sb.logp, T * B * 256 * 4, hipMemcpyDefault, s));
+    RET(gen_rows_err_launch(c.pl ? c.b.gerr : nullptr, sb.sticky, s));
+    SRNN_CHECK_HIP(hipMemcpyAsync((void*)se.host_err, sb.sticky, sizeof(int),
+                                  hipMemcpyDeviceToHost, s));
+    return 0;
+}
+
+int session_chunk(Session& se, const SrnnGenChunk& ck, hipStream_t user) {
+    if (se.poisoned) return se.refused();
+    if (*se.host_err) return se.poison_err_word();
+    RET(session_check(se, ck));
+    if (session_queue(se, ck, user)) return se.poison();
+    const int64_t T = (int64_t)ck.n_frames * se.c.L;
+    for (int64_t& v : se.steps) v += T;
+    se.st.chunks++;
+    return 0;
+}
+
+int session_sync(Session& se) {
+    if (se.poisoned) return se.refused();
+    if (hipStreamSynchronize(se.c.s) != hipSuccess) {
+        srnn_set_error("generate: %s", hipGetErrorString(hipGetLastError()));
+        return se.poison();
+    }
+    se.staged = false;
+    if (*se.host_err) return se.poison_err_word();
+    return 0;
+}
+
+int session_set_rows(Session& se, const int32_t* rows, int n, const void* records, size_t bytes,
+                     hipStream_t user) {
+    if (se.poisoned) return se.refused();
+    Ctx& c = se.c;
+    const int B = se.rq.n_seqs;
+    const size_t rb = (size_t)c.rw * 4;
+    SRNN_REQUIRE(rows && records && n >= 1 && n <= B, "gen_session: bad args");
+    SRNN_REQUIRE(bytes == rb * (size_t)n && ((uintptr_t)records & 7) == 0,
+                 "generate: state of %zu bytes, this model / batch / fold layout needs %zu", bytes,
+                 rb * (size_t)n);
+    std::vector<char> seen((size_t)B, 0);
+    for (int i = 0; i < n; ++i) {
+        SRNN_REQUIRE(rows[i] >= 0 && rows[i] < B && !seen[rows[i]],
+                     "gen_session: rows must be distinct values in [0, %d)", B);
+        seen[rows[i]] = 1;
+    }
+    hipStream_t s = c.s;
+    if (hipEventRecord(c.gs.ev, user) != hipSuccess ||
+        hipStreamWaitEvent(s, c.gs.ev, 0) != hipSuccess) {
+        srnn_set_error("gen_session: %s", hipGetErrorString(hipGetLastError()));
+        return se.poison();
+    }
+    // headers first: nothing is written where one is not of the session's layout
+    if (const int rc = gen_check_headers(c, records, n, s)) return rc == 1 ? 1 : se.poison();
+    se.staged = false;
+    std::vector<int64_t> cnt((size_t)n);
+    bool ok = hipMemcpy2DAsync(cnt.data(), 8, (const char*)records + 32, rb, 8, n,
+                               hipMemcpyDeviceToHost, s) == hipSuccess &&
+              hipStreamSynchronize(s) == hipSuccess;
+    if (ok)
+        for (int i = 0; i < n; ++i)
+            SRNN_REQUIRE(cnt[i] >= 0, "gen_session: record %d has a negative step count", i);
+    for (int i = 0; ok && i < n; ++i)
+        ok = hipMemcpyAsync((char*)se.sb.records + rb * rows[i], (const char*)records + rb * i, rb,
+                            hipMemcpyDeviceToDevice, s) == hipSuccess;
+    if (!ok || hipStreamSynchronize(s) != hipSuccess) {
+        srnn_set_error("gen_session: replacing rows: %s", hipGetErrorString(hipGetLastError()));
+        return se.poison();
+    }
+    for (int i = 0; i < n; ++i) se.steps[rows[i]] = cnt[i];
+    return 0;
+}
+
+int session_close(Session* se) {
+    if (!se) return 0;
+    int rc = 0;
+    // the stream is drained before anything is released, on every path
+    if (se->c.s && hipStreamSynchronize(se->c.s) != hipSuccess) {
+        srnn_set_error("gen_session: close: %s", hipGetErrorString(hipGetLastError()));
+        rc = 2;
+    }
+    for (int k = 0; k < 2; ++k) {
+        if (se->exec[k]) (void)hipGraphExecDestroy(se->exec[k]);
+        if (se->graph[k]) (void)hipGraphDestroy(se->graph[k]);
+    }
+    if (se->host_err) (void)hipHostFree((void*)se->host_err);
+    delete se;
+    return rc;
+}
+
+// the opaque handle of the C ABI is a Session
+inline Session* session_of(const SrnnGenSession* h) { return (Session*)h; }
+
 }  // namespace
+
+extern "C" int srnn_gen_session_bytes(const SrnnModel* m, int n_seqs, int max_frames, int level,
+                                      int flags, size_t* bytes) {
+    SRNN_REQUIRE(bytes, "gen_session: bad args");
+    SessBufs sb;
+    return session_carve(m, n_seqs, max_frames, level, flags, GenSwitches::read(), nullptr, &sb,
+                         bytes);
+}
+
+extern "C" int srnn_gen_session_open(const SrnnModel* m, int n_seqs, int max_frames, int level,
+                                     uint64_t seed, int row0, int flags, void* arena,
+                                     size_t arena_bytes, void* stream, SrnnGenSession** out) {
+    SRNN_REQUIRE(out, "gen_session: bad args");
+    *out = nullptr;
+    SRNN_REQUIRE(m && arena && ((uintptr_t)arena & (ALIGN - 1)) == 0 && row0 >= 0,
+                 "gen_session: the arena must be 256-byte aligned, the row offset >= 0");
+    size_t need = 0;
+    SessBufs sb;
+    RET(session_carve(m, n_seqs, max_frames, level, flags, GenSwitches::read(), nullptr, &sb,
+                      &need));
+    SRNN_REQUIRE(arena_bytes >= need, "gen_session: arena %zu < %zu", arena_bytes, need);
+    Session* se = new Session(*m, n_seqs, max_frames, level, seed, row0, flags,
+                              (hipStream_t)stream);
+    const int rc = session_open(*se, (char*)arena, arena_bytes);
+    if (rc) {
+        // (the open's error text stays: the drain sets one only where it fails itself)
+        session_close(se);
+        return rc;
+    }
+    *out = (SrnnGenSession*)se;
+    return 0;
+}
+
+extern "C" int srnn_gen_session_chunk(SrnnGenSession* s, const SrnnGenChunk* chunk,
+                                      void* stream) {
+    SRNN_REQUIRE(s && chunk, "gen_session: bad args");
+    return session_chunk(*session_of(s), *chunk, (hipStream_t)stream);
+}
+
+extern "C" int srnn_gen_session_sync(SrnnGenSession* s) {
+    SRNN_REQUIRE(s, "gen_session: bad args");
+    return session_sync(*session_of(s));
+}
+
+extern "C" int srnn_gen_session_state_get(SrnnGenSession* s, void* records, size_t bytes) {
+    SRNN_REQUIRE(s && records, "gen_session: bad args");
+    Session& se = *session_of(s);
+    if (se.poisoned) return se.refused();
+    const size_t sb = (size_t)se.c.rw * 4 * (size_t)se.rq.n_seqs;
+    SRNN_REQUIRE(bytes == sb,
+                 "generate: state of %zu bytes, this model / batch / fold layout needs %zu", bytes,
+                 sb);
+    if (hipMemcpyAsync(records, se.sb.records, sb, hipMemcpyDefault, se.c.s) != hipSuccess) {
+        srnn_set_error("gen_session: reading the records: %s",
+                       hipGetErrorString(hipGetLastError()));
+        return se.poison();
+    }
+    return session_sync(se);
+}
+
+extern "C" int srnn_gen_session_state_set_rows(SrnnGenSession* s, const int32_t* rows, int n,
+                                               const void* records, size_t bytes, void* stream) {
+    SRNN_REQUIRE(s, "gen_session: bad args");
+    return session_set_rows(*session_of(s), rows, n, records, bytes, (hipStream_t)stream);
+}
+
+extern "C" int srnn_gen_session_stats(const SrnnGenSession* s, SrnnGenSessionStats* stats) {
+    SRNN_REQUIRE(s && stats, "gen_session: bad args");
+    const Session& se = *session_of(s);
+    *stats = se.st;
+    stats->steps_min = stats->steps_max = se.steps[0];
+    for (const int64_t v : se.steps) {
+        stats->steps_min = v < stats->steps_min ? v : stats->steps_min;
+        stats->steps_max = v > stats->steps_max ? v : stats->steps_max;
+    }
+    return 0;
+}
+
+extern "C" int srnn_gen_session_close(SrnnGenSession* s) { return session_close(session_of(s)); }
 
 // rows per group of the persistent sample loop at sampling-control level `level` (0: the plain
 // plan; 1: temperature / top_k / a forced prefix, 64 B more LDS; 2: with top_p, 96 B more), or

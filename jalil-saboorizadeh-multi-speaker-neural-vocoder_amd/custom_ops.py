@@ -19,6 +19,11 @@ The drop-in classes call these ops, so the registered ops ARE the product path:
   srnn::generate_stream         the loop over a chunk of a stream: carried state in / out, a
                                 Philox step origin, a forced prefix; optional controls
   srnn::sample_rows             the loops' row sampler on caller-chosen logits
+  srnn::gen_session_chunk       one chunk of a generation session (model.GenSession): the loop
+                                from the session's kept weights, workspace, records and graph
+  srnn::gen_session_state       the session's records
+(gen_session_open / _replace / _stats / _close are plain functions: they return or take the
+session's handle and no tensor comes back)
 
 Every op has a fake (meta) kernel, so FakeTensor / torch.compile tracing sees shapes without
 running HIP code, and the differentiable ones have their autograd formula attached with
@@ -671,6 +676,141 @@ def _(weights, meta, n_seqs):
     return weights[0].new_empty((n_seqs, gen_state_row_bytes(meta)), dtype=torch.uint8)
 
 
+# ------------------------------------------------------------------ generation sessions
+def gen_session_open(weights, meta, n_seqs, max_frames, level, seed, row_offset, flags):
+    """Opens a library session (srnn_gen_session_open) over model.generation_weights' tensors:
+    returns (handle, arena).  The handle is a plain int; the caller keeps `arena` AND `weights`
+    alive, and unchanged, until gen_session_close(handle) -- the session reads both."""
+    import ctypes
+    import model
+    if n_seqs < 1 or max_frames < 1 or level not in (0, 1, 2):
+        raise ValueError('gen_session_open: n_seqs and max_frames must be >= 1, level 0, 1 or 2')
+    m = model.srnn_model_struct(weights, meta)
+    dev = weights[0].device
+    sz = ctypes.c_size_t(0)
+    H.lib().call('srnn_gen_session_bytes', ctypes.byref(m), n_seqs, max_frames, level, flags,
+                 ctypes.byref(sz))
+    arena = torch.empty(sz.value, device=dev, dtype=torch.uint8)
+    handle = ctypes.c_void_p(None)
+    H.lib().call('srnn_gen_session_open', ctypes.byref(m), n_seqs, max_frames, level,
+                 int(seed) & ((1 << 64) - 1), int(row_offset), flags, H.ptr(arena), sz.value,
+                 H.stream(), ctypes.byref(handle))
+    return handle.value, arena
+
+
+def gen_session_close(handle):
+    """Drains and releases a session (srnn_gen_session_close); its arena may then be freed."""
+    H.lib().call('srnn_gen_session_close', handle)
+
+
+def gen_session_stats(handle):
+    """The session's diagnostic counters (srnn_gen_session_stats) as a dict."""
+    import ctypes
+    st = H.SrnnGenSessionStats()
+    H.lib().call('srnn_gen_session_stats', handle, ctypes.byref(st))
+    return {n: int(getattr(st, n)) for n, _ in st._fields_}
+
+
+@torch.library.custom_op('srnn::gen_session_chunk', mutates_args=())
+def gen_session_chunk(handle: int, lookback: int, cond: Tensor, row_bias: Optional[Tensor],
+                      temperature: Optional[Tensor], top_k: Optional[Tensor],
+                      top_p: Optional[Tensor], prefix: Optional[Tensor],
+                      prefix_len: Optional[Tensor], noise_row: Optional[Tensor],
+                      noise: Optional[Tensor], return_logp: bool) -> tuple[Tensor, Tensor]:
+    """One chunk of a session (srnn_gen_session_chunk, then srnn_gen_session_sync): cond
+    (n_seqs, frames, C) float32; every other tensor optional, None = as in the previous chunk
+    (prefix: nothing forced): row_bias (n_seqs, D) float32, temperature / top_k / top_p as
+    srnn::generate_ctrl_p takes them, prefix (n_seqs, P <= T) int64 with prefix_len (n_seqs,)
+    int32 (None = P), noise_row a HOST (n_seqs,) int32 tensor of Philox rows, noise
+    (T, n_seqs, 256) float32 for a session opened for replayed noise.  Returns (the chunk's
+    sample indices (n_seqs, T) int64, log-probs (T, n_seqs, 256) or empty), T = frames *
+    lookback.  The library checks the chunk against the session before it queues anything."""
+    import ctypes
+    op = 'gen_session_chunk'
+    if (cond.dim() != 3 or cond.dtype != torch.float32 or not cond.is_cuda or
+            not cond.is_contiguous()):
+        raise ValueError(op + ': cond must be a contiguous (n_seqs, frames, C) float32 device '
+                         'tensor')
+    n_seqs, frames, dev = cond.shape[0], cond.shape[1], cond.device
+    T = frames * lookback
+    _check_rows(op, n_seqs, dev,
+                *[(n, t, dt) for n, t, dt in (('temperature', temperature, torch.float32),
+                                              ('top_k', top_k, torch.int32),
+                                              ('top_p', top_p, torch.float32),
+                                              ('prefix_len', prefix_len, torch.int32))
+                  if t is not None])
+    if noise_row is not None:
+        _check_rows(op, n_seqs, torch.device('cpu'), ('noise_row', noise_row, torch.int32))
+    if row_bias is not None and (row_bias.dim() != 2 or row_bias.shape[0] != n_seqs or
+                                 row_bias.dtype != torch.float32 or row_bias.device != dev or
+                                 not row_bias.is_contiguous()):
+        raise ValueError(op + ': row_bias must be a contiguous (n_seqs, D) float32 tensor on %s'
+                         % dev)
+    if noise is not None and (noise.shape != (T, n_seqs, 256) or noise.dtype != torch.float32 or
+                              noise.device != dev or not noise.is_contiguous()):
+        raise ValueError(op + ': noise must be a contiguous (%d, %d, 256) float32 tensor on %s'
+                         % (T, n_seqs, dev))
+    ck = H.SrnnGenChunk()
+    if prefix_len is not None and prefix is None:
+        raise ValueError(op + ': prefix_len without a prefix')
+    if prefix is not None:
+        if (prefix.dim() != 2 or prefix.shape[0] != n_seqs or not 1 <= prefix.shape[1] <= T or
+                prefix.dtype != torch.int64 or prefix.device != dev):
+            raise ValueError(op + ': prefix must be an (n_seqs, 1..%d) int64 tensor on %s'
+                             % (T, dev))
+        P = prefix.shape[1]
+        prefix = prefix.clamp(0, 255).contiguous()
+        n_forced = (prefix_len.clamp(0, P) if prefix_len is not None else
+                    torch.full((n_seqs,), P, dtype=torch.int32, device=dev)).contiguous()
+        ck.prefix, ck.prefix_cols, ck.n_forced = H.ptr(prefix), P, H.ptr(n_forced)
+    seq = torch.empty((n_seqs, T), dtype=torch.long, device=dev)
+    logp = torch.empty((T, n_seqs, 256) if return_logp else (0,), device=dev)
+    ck.n_frames, ck.cond, ck.row_bias = frames, H.ptr(cond), H.ptr(row_bias)
+    ck.temperature, ck.top_k, ck.top_p = H.ptr(temperature), H.ptr(top_k), H.ptr(top_p)
+    ck.noise_row, ck.noise = H.ptr(noise_row), H.ptr(noise)
+    ck.seq_out, ck.logp_out = H.ptr(seq), H.ptr(logp) if return_logp else None
+    H.lib().call('srnn_gen_session_chunk', handle, ctypes.byref(ck), H.stream())
+    H.lib().call('srnn_gen_session_sync', handle)
+    return seq, logp
+
+
+@gen_session_chunk.register_fake
+def _(handle, lookback, cond, row_bias, temperature, top_k, top_p, prefix, prefix_len, noise_row,
+      noise, return_logp):
+    n_seqs, T = cond.shape[0], cond.shape[1] * lookback
+    return (cond.new_empty((n_seqs, T), dtype=torch.long),
+            cond.new_empty((T, n_seqs, 256) if return_logp else (0,)))
+
+
+@torch.library.custom_op('srnn::gen_session_state', mutates_args=())
+def gen_session_state(handle: int, like: Tensor, n_seqs: int, row_bytes: int) -> Tensor:
+    """The session's records (srnn_gen_session_state_get) as an (n_seqs, row_bytes) uint8 tensor
+    on `like`'s device, after the chunks queued so far."""
+    out = torch.empty((n_seqs, row_bytes), dtype=torch.uint8, device=like.device)
+    H.lib().call('srnn_gen_session_state_get', handle, H.ptr(out), out.numel())
+    return out
+
+
+@gen_session_state.register_fake
+def _(handle, like, n_seqs, row_bytes):
+    return like.new_empty((n_seqs, row_bytes), dtype=torch.uint8)
+
+
+def gen_session_replace(handle, rows, records):
+    """Replaces the records of the session's rows `rows` (a host (n,) int32 tensor of distinct
+    row numbers) by `records` ((n, row_bytes) uint8 on the device): srnn_gen_session_state_set_rows,
+    which checks every header before it writes anything."""
+    if (rows.dtype != torch.int32 or rows.dim() != 1 or rows.is_cuda or not rows.is_contiguous()):
+        raise ValueError('gen_session_replace: rows must be a contiguous host (n,) int32 tensor')
+    if (records.dtype != torch.uint8 or records.dim() != 2 or not records.is_cuda or
+            records.shape[0] != rows.shape[0]):
+        raise ValueError('gen_session_replace: records must be an (n, row_bytes) uint8 device '
+                         'tensor, one record per row number')
+    records = records.contiguous()
+    H.lib().call('srnn_gen_session_state_set_rows', handle, H.ptr(rows), rows.shape[0],
+                 H.ptr(records), records.numel(), H.stream())
+
+
 @torch.library.custom_op('srnn::sample_rows', mutates_args=())
 def sample_rows(logits: Tensor, noise: Optional[Tensor], seed: int, row0: int, step: int,
                 temperature: Optional[Tensor], top_k: Optional[Tensor],
@@ -715,4 +855,5 @@ def _(logits, noise, seed, row0, step, temperature, top_k, top_p, return_logp):
 
 OPS = ('tier_fwd', 'tier_bwd', 'mlp_fwd', 'mlp_bwd', 'nll_bits', 'nll_bits_bwd', 'upsample',
        'upsample_bwd', 'dequant', 'adam_clip_', 'step_advance_', 'generate', 'generate_ctrl',
-       'generate_ctrl_p', 'generate_stream', 'generate_rows', 'gen_state_fresh', 'sample_rows')
+       'generate_ctrl_p', 'generate_stream', 'generate_rows', 'gen_state_fresh', 'sample_rows',
+       'gen_session_chunk', 'gen_session_state')

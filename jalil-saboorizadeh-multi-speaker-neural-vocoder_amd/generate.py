@@ -26,6 +26,8 @@ At the defaults the run is the reference's draw, bit for bit as before.
 per call through Generator.stream, the recurrent state carried from call to call: the same
 WAV, byte for byte, with the sampler's host noise bounded by the chunk (single-process runs;
 rank-sharded batches are generated whole).
+--session True (with --chunk_frames, or with --batch_files True --slots) runs those chunks through
+one generation session (Generator.session): the same WAVs, without each call's set-up.
 """
 import argparse
 import os
@@ -75,14 +77,16 @@ default_params = {
     'top_p': 1.0,
     'chunk_frames': 0,
     'slots': 0,
+    'session': False,
 }
 
 
-def run_generator(gen, n_seqs, sample_length, cond, spk, chunk_frames, **kw):
+def run_generator(gen, n_seqs, sample_length, cond, spk, chunk_frames, session=False, **kw):
     """Generator.__call__, or the concatenated blocks of Generator.stream when chunk_frames is
-    set (equal bit for bit)."""
+    set (equal bit for bit), through one session when asked."""
     if chunk_frames > 0:
-        return torch.cat(list(gen.stream(n_seqs, cond, spk, chunk_frames, **kw)), dim=1)
+        return torch.cat(list(gen.stream(n_seqs, cond, spk, chunk_frames, session=session,
+                                         **kw)), dim=1)
     return gen(n_seqs, sample_length, cond, spk, **kw)
 
 
@@ -195,6 +199,8 @@ def main(frame_sizes, **params):
             sys.exit('--slots serves with the device sampler only: pass --sampler philox.')
         if world > 1:
             sys.exit('--slots runs in a single process.')
+    if params['session'] and not (params['chunk_frames'] > 0 or params['slots'] > 0):
+        sys.exit('--session goes with --chunk_frames N or --slots N.')
     if params['batch_files']:
         init_random_seed(params['seed'], use_cuda)
         model = build_model(params, spk_dim, use_cuda)
@@ -217,7 +223,7 @@ def main(frame_sizes, **params):
                     for j in range(len(jobs)) for i in range(n)]
             out = np.zeros((len(rows), n_cond * model.lookback), dtype=np.float32)
             for u, samples in gen.serve(reqs, params['slots'], params['chunk_frames'] or 32,
-                                        seed=params['seed']):
+                                        seed=params['seed'], session=params['session']):
                 out[u, :samples.shape[0]] = samples.numpy()
         elif world > 1:
             # rank-sharded: contiguous row shards gathered at the end (rows
@@ -231,8 +237,8 @@ def main(frame_sizes, **params):
                                  seq_len=params['sample_length'], **ctrl).numpy()[:len(rows)]
         else:
             out = run_generator(gen, len(rows), params['sample_length'], rows, spks,
-                                params['chunk_frames'], sampler=params['sampler'],
-                                seed=params['seed'], **ctrl).numpy()
+                                params['chunk_frames'], session=params['session'],
+                                sampler=params['sampler'], seed=params['seed'], **ctrl).numpy()
         if rank != 0:
             return
         L = model.lookback
@@ -251,8 +257,9 @@ def main(frame_sizes, **params):
         print('Generating file', fname)
         gen = Generator(model, use_cuda)
         samples = run_generator(gen, params['n_samples'], params['sample_length'], cond, speaker,
-                                params['chunk_frames'], sampler=params['sampler'],
-                                seed=params['seed'], temperature=params['temperature'],
+                                params['chunk_frames'], session=params['session'],
+                                sampler=params['sampler'], seed=params['seed'],
+                                temperature=params['temperature'],
                                 top_k=params['top_k'], top_p=params['top_p']).numpy()
         for i in range(params['n_samples']):
             write_wav(fname, samples[i, :], sr=params['sample_rate'])
@@ -283,7 +290,7 @@ def build_parser():
                       ('cond_list', str), ('spk_list', str), ('sampler', str),
                       ('batch_files', parse_bool), ('compute_dtype', str),
                       ('temperature', float), ('top_k', int), ('top_p', float),
-                      ('chunk_frames', int), ('slots', int)):
+                      ('chunk_frames', int), ('slots', int), ('session', parse_bool)):
         p.add_argument('--' + name, type=typ)
     # gen.sh passes --results_path (generate.py has no such option; accepted and ignored)
     p.add_argument('--results_path', type=str)

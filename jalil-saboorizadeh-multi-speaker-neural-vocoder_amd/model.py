@@ -1246,6 +1246,208 @@ def forced_prefix(model, n_seqs, T, prefix, prefix_len):
     return p, torch.from_numpy(a.astype(np.int32))
 
 
+def session_chunk_check(level, max_frames, frames, have_spk, temperature=None, top_k=None,
+                        top_p=None, prefix=None):
+    """What GenSession.chunk refuses before anything runs (a pure host function; the library
+    makes the same checks): `frames` outside [1, max_frames], a control or a prefix above the
+    session's `level` (temperature / top_k / prefix need 1, top_p needs 2), no spk on the first
+    chunk (have_spk: an earlier chunk gave one, or this one does).  Raises ValueError."""
+    if not 1 <= int(frames) <= int(max_frames):
+        raise ValueError('GenSession.chunk: %d frames, the session was opened for 1..%d'
+                         % (frames, max_frames))
+    need = 2 if top_p is not None else 1 if (temperature is not None or top_k is not None or
+                                             prefix is not None) else 0
+    if need > level:
+        raise ValueError('GenSession.chunk: %s needs a session of level >= %d, this one is of '
+                         'level %d' % ('top_p' if need == 2 else 'temperature / top_k / a prefix',
+                                       need, level))
+    if not have_spk:
+        raise ValueError('GenSession.chunk: the first chunk must give spk')
+
+
+def session_advance(steps, frames, lookback, philox=True):
+    """The host mirror of a session's per-row step counts after a chunk of `frames` frames (a
+    pure host function): steps + frames * lookback, an int64 tensor.  Under device noise
+    (philox) a row whose count would pass the 32-bit Philox step counter raises ValueError, as
+    the library refuses the chunk."""
+    steps = torch.as_tensor(steps, dtype=torch.int64).reshape(-1)
+    T = int(frames) * int(lookback)
+    if philox and steps.numel() and int(steps.max()) + T > 0xFFFFFFFF:
+        b = int(steps.argmax())
+        raise ValueError('GenSession.chunk: row %d: step0 %d + %d steps overflow the 32-bit '
+                         'Philox step counter' % (b, int(steps[b]), T))
+    return steps + T
+
+
+class GenSession:
+    """A generation session (Generator.session; srnn_gen_session_*): consecutive chunks of one
+    (model, n_seqs, control level, switches) without a call's set-up.  The generation weight
+    layouts, the folded tick weights, the workspace, the rows' records and the captured blocks
+    are made once and kept; a chunk copies its inputs in, runs and copies its samples out.
+
+    A session SNAPSHOTS generation_weights(model) when it is opened: later updates of the
+    model's parameters are not seen (open a new session after training steps).  The speaker
+    embedding behind `spk` is the exception: it is read from the model by each chunk that gives
+    spk.  What a chunk generates is what the Generator.__call__ with state=<the session's
+    state>, stream_ids=<the rows' ids> and the same inputs generates, bit for bit.
+
+    steps   (n_seqs,) int64 host tensor: the steps each row has completed.
+    last_sequences   the last chunk's sample indices, (n_seqs, frames * lookback) on the device.
+    Use after close() raises RuntimeError; a session is a context manager."""
+
+    def __init__(self, generator, n_seqs, max_frames, dtype=None, level=0, seed=0,
+                 persistent=True, use_graph=True, return_logp=False, replay_noise=False,
+                 row_offset=0):
+        import custom_ops
+        model = generator.model
+        self.model = model
+        self.n_seqs, self.max_frames, self.level = int(n_seqs), int(max_frames), int(level)
+        self.return_logp, self.replay_noise = bool(return_logp), bool(replay_noise)
+        self._dev = next(model.parameters()).device
+        H.need_cuda(torch.empty(0, device=self._dev))
+        self._handle = None
+        self.weights, self.meta = generation_weights(model, dtype)
+        flags = ((H.GEN_SESSION_GRAPH if use_graph else 0) |
+                 (0 if persistent else H.GEN_SESSION_PER_SAMPLE) |
+                 (H.GEN_SESSION_LOGP if return_logp else 0) |
+                 (H.GEN_SESSION_NOISE if replay_noise else 0))
+        with torch.no_grad():
+            self._handle, self._arena = custom_ops.gen_session_open(
+                self.weights, self.meta, self.n_seqs, self.max_frames, self.level, seed,
+                row_offset, flags)
+        self.steps = torch.zeros(self.n_seqs, dtype=torch.int64)
+        self.last_sequences = None
+        self._have_spk = False
+        self._ctl = [1.0, 0, 1.0]            # temperature, top_k, top_p of the previous chunk
+
+    def _live(self):
+        if self._handle is None:
+            raise RuntimeError('GenSession: the session is closed')
+        return self._handle
+
+    def chunk(self, cond, spk=None, temperature=None, top_k=None, top_p=None, prefix=None,
+              prefix_len=None, stream_ids=None, noise=None):
+        """Generates cond's frames ((frames, C) shared or (n_seqs, frames, C), at most
+        max_frames) from where the rows stand, and returns what Generator.__call__ returns:
+        host float32 (n_seqs, frames * lookback) samples, with return_logp (samples, log-probs
+        (n_seqs, T, Q)).  spk, temperature, top_k, top_p and stream_ids at None stay as in the
+        previous chunk (at first: required, 1, off, 1, row_offset + b); prefix / prefix_len
+        force this chunk only.  noise: this chunk's (T, n_seqs, Q) Exp(1) draws, given exactly
+        when the session was opened with replay_noise."""
+        handle = self._live()
+        model, n_seqs, dev = self.model, self.n_seqs, self._dev
+        cond = torch.as_tensor(np.asarray(cond) if not torch.is_tensor(cond) else cond)
+        if cond.dim() == 2:
+            cond = cond.unsqueeze(0).expand(n_seqs, *cond.shape)
+        if cond.dim() != 3 or cond.shape[0] != n_seqs:
+            raise ValueError('GenSession.chunk: cond must be (frames, C) or (%d, frames, C)'
+                             % n_seqs)
+        frames = cond.shape[1]
+        session_chunk_check(self.level, self.max_frames, frames,
+                            self._have_spk or spk is not None, temperature, top_k, top_p, prefix)
+        L, Q = model.lookback, model.q_levels
+        T = frames * L
+        if (noise is not None) != self.replay_noise:
+            raise ValueError('GenSession.chunk: noise is given by exactly the chunks of a '
+                             'session opened with replay_noise=True')
+        steps = session_advance(self.steps, frames, L, not self.replay_noise)
+        row_bias = None
+        if spk is not None:
+            spk = torch.as_tensor(np.asarray(spk) if not torch.is_tensor(spk) else spk).reshape(-1)
+            if spk.numel() == 1:
+                spk = spk.expand(n_seqs)
+            row_bias = top_row_bias(model, spk.to(dev, torch.long).contiguous())
+        tau = k = p = None
+        if temperature is not None or top_k is not None:
+            ctl = [self._ctl[0] if temperature is None else temperature,
+                   self._ctl[1] if top_k is None else top_k]
+            got = sampling_controls(n_seqs, ctl[0], ctl[1], Q)
+            tau, k = got if got is not None else (torch.ones(n_seqs, dtype=torch.float32),
+                                                  torch.zeros(n_seqs, dtype=torch.int32))
+            self._ctl[:2] = ctl
+        if top_p is not None:
+            p = nucleus_control(n_seqs, top_p)
+            p = p if p is not None else torch.ones(n_seqs, dtype=torch.float32)
+            self._ctl[2] = top_p
+        prefix, prefix_len = forced_prefix(model, n_seqs, T, prefix, prefix_len)
+        if prefix is not None and prefix.shape[1] == 0:
+            prefix = prefix_len = None
+        ids = stream_rows(n_seqs, stream_ids)
+        if noise is not None:
+            noise = torch.as_tensor(noise).to(dev, torch.float32).contiguous()
+            if noise.shape != (T, n_seqs, Q):
+                raise ValueError('GenSession.chunk: noise must be (T, n_seqs, Q)')
+        on = (lambda t: None if t is None else t.to(dev))
+        with torch.no_grad():
+            seq, logp = torch.ops.srnn.gen_session_chunk(
+                handle, L, cond.to(dev, torch.float32).contiguous(), row_bias, on(tau), on(k),
+                on(p), on(prefix), on(prefix_len), ids, noise, self.return_logp)
+        self.steps = steps
+        self._have_spk = True
+        self.last_sequences = seq
+        out = model.dequantize(seq, Q).cpu()
+        if self.return_logp:
+            return out, logp.permute(1, 0, 2).contiguous()
+        return out
+
+    def state(self):
+        """The rows' GenState after the chunks so far (a copy: the session keeps its own)."""
+        layout = gen_state_layout(self.meta)
+        blob = torch.ops.srnn.gen_session_state(self._live(), self.weights[0], self.n_seqs,
+                                                layout[5])
+        return GenState(blob, layout, self.steps.clone())
+
+    def replace(self, rows, state):
+        """Rows `rows` (distinct row numbers) continue from `state`'s rows, in order, step
+        counts included -- fresh_state() records start new streams there.  The library checks
+        every record's header against the session's layout before it writes any."""
+        import custom_ops
+        handle = self._live()
+        idx = torch.as_tensor(rows, dtype=torch.long).reshape(-1).cpu()
+        if not isinstance(state, GenState):
+            raise TypeError('GenSession.replace: state must be a GenState')
+        if idx.numel() != state.n_seqs or idx.numel() == 0:
+            raise ValueError('GenSession.replace: %d row numbers for %d rows'
+                             % (idx.numel(), state.n_seqs))
+        if int(idx.min()) < 0 or int(idx.max()) >= self.n_seqs:
+            raise IndexError('GenSession.replace: row numbers must lie in [0, %d)' % self.n_seqs)
+        if idx.unique().numel() != idx.numel():
+            raise ValueError('GenSession.replace: row numbers must be distinct')
+        custom_ops.gen_session_replace(handle, idx.to(torch.int32).contiguous(),
+                                       state.blob.to(self._dev))
+        self.steps = self.steps.clone()
+        self.steps[idx] = state.steps
+
+    def stats(self):
+        """{'prepares', 'graphs_captured', 'graph_launches', 'eager_blocks', 'chunks',
+        'steps_min', 'steps_max'}: the library's diagnostic counters of this session."""
+        import custom_ops
+        return custom_ops.gen_session_stats(self._live())
+
+    def close(self):
+        """Drains the session and releases it; further use raises.  Closing twice is allowed."""
+        import custom_ops
+        if self._handle is not None:
+            handle, self._handle = self._handle, None
+            try:
+                custom_ops.gen_session_close(handle)
+            finally:
+                self._arena = self.weights = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Generator(Runner):
     """model.py:439-520: autoregressive generation, the whole loop on the device.
 
@@ -1430,8 +1632,21 @@ class Generator(Runner):
             blob = torch.ops.srnn.gen_state_fresh(weights, meta, n_seqs)
         return GenState(blob, gen_state_layout(meta), torch.zeros(n_seqs, dtype=torch.int64))
 
+    def session(self, n_seqs, max_frames, dtype=None, level=0, seed=0, persistent=True,
+                use_graph=True, return_logp=False, replay_noise=False, row_offset=0):
+        """A GenSession of n_seqs rows for chunks of at most max_frames conditioning frames:
+        the generation weights (SNAPSHOT here: later parameter updates are not seen), the
+        workspace, the rows' records -- fresh ones -- and the captured blocks are kept between
+        its chunks.  level: the sampling controls its chunks may carry (0 none, 1 temperature /
+        top_k / prefix, 2 with top_p); seed: the Philox seed of every chunk; replay_noise: every
+        chunk brings its noise (sampler='torch' streams), else the device draws it;
+        row_offset: the Philox row of row b is row_offset + b until a chunk gives stream_ids.
+        dtype, persistent, use_graph, return_logp: as in __call__."""
+        return GenSession(self, n_seqs, max_frames, dtype, level, seed, persistent, use_graph,
+                          return_logp, replay_noise, row_offset)
+
     def serve(self, requests, slots, chunk_frames, seed=0, dtype=None, persistent=True,
-              use_graph=True):
+              use_graph=True, session=False):
         """Continuous batching: runs `requests` -- dicts with cond (F_u, C) and spk, optionally
         stream_id (default: the request's position), temperature, top_k, top_p -- through `slots`
         rows by serve_plan's calls (sampler='philox' only), and yields (position, host float32
@@ -1439,7 +1654,9 @@ class Generator(Runner):
         one-shot self(slots, 0, cond_u, spk_u, sampler='philox', seed=seed,
         row_offset=stream_id_u, <u's controls>), sample for sample.  If any request carries a
         control, every call passes per-row control arrays (defaults for the other rows).
-        self.last_serve: {'calls', 'frames' (per call), 'row_frames'} of the run."""
+        self.last_serve: {'calls', 'frames' (per call), 'row_frames'} of the run.
+        session=True runs the same plan as the chunks of one GenSession, new requests replacing
+        their rows' records by fresh ones: the same yields, without the calls' set-up."""
         requests = list(requests)
         slots = int(slots)
         conds = []
@@ -1459,6 +1676,10 @@ class Generator(Runner):
             return
         C = conds[0].shape[1]
         fresh = self.fresh_state(slots, dtype)
+        if session:
+            yield from self._serve_session(requests, conds, plan, ids, level, fresh, seed, dtype,
+                                           persistent, use_graph)
+            return
         state = fresh
         parts = {}
         for n, rows in plan:
@@ -1492,7 +1713,97 @@ class Generator(Runner):
                 if f1 == conds[u].shape[0]:
                     yield u, torch.cat(parts.pop(u))
 
-    def stream(self, n_seqs, cond, spk, chunk_frames, state=None, **kw):
+    def _serve_session(self, requests, conds, plan, ids, level, fresh, seed, dtype, persistent,
+                       use_graph):
+        """serve's calls as the chunks of one session (same plan, same per-row inputs)."""
+        slots, C, L = fresh.n_seqs, conds[0].shape[1], self.model.lookback
+        parts = {}
+        last_spk = None
+        with self.session(slots, max(n for n, _ in plan), dtype=dtype, level=level, seed=seed,
+                          persistent=persistent, use_graph=use_graph) as sess:
+            for n, rows in plan:
+                cond = torch.zeros(slots, n, C)
+                spk = torch.zeros(slots, dtype=torch.long)
+                sid = torch.zeros(slots, dtype=torch.int64)
+                tau, k, p = [1.0] * slots, [0] * slots, [1.0] * slots
+                for s, (u, f0, f1, _) in enumerate(rows):
+                    if u is None:
+                        continue
+                    rq = requests[u]
+                    cond[s, :f1 - f0] = conds[u][f0:f1]
+                    spk[s] = int(torch.as_tensor(rq['spk']).reshape(-1)[0])
+                    sid[s] = ids[u]
+                    tau[s], k[s], p[s] = (rq.get('temperature', 1.0), rq.get('top_k', 0),
+                                          rq.get('top_p', 1.0))
+                # (a row that has done no step already stands on a fresh record)
+                new = [s for s, row in enumerate(rows) if row[3] and int(sess.steps[s]) != 0]
+                if new:
+                    sess.replace(new, fresh.rows(new))
+                ctl = {}
+                if level >= 1:
+                    ctl.update(temperature=tau, top_k=k)
+                if level >= 2:
+                    ctl.update(top_p=p)
+                same_spk = last_spk is not None and torch.equal(spk, last_spk)
+                out = sess.chunk(cond, spk=None if same_spk else spk, stream_ids=sid, **ctl)
+                last_spk = spk
+                self.last_serve['calls'] += 1
+                self.last_serve['frames'].append(n)
+                self.last_serve['row_frames'] += slots * n
+                for s, (u, f0, f1, _) in enumerate(rows):
+                    if u is None:
+                        continue
+                    parts.setdefault(u, []).append(out[s, :(f1 - f0) * L])
+                    if f1 == conds[u].shape[0]:
+                        yield u, torch.cat(parts.pop(u))
+
+    def _stream_session(self, n_seqs, cond, spk, chunk_frames, state, kw):
+        """stream's calls as the chunks of one session."""
+        kw = dict(kw)
+        sampler, noise = kw.pop('sampler', 'torch'), kw.pop('noise', None)
+        logp = bool(kw.pop('return_logp', False))
+        tau, k, p = kw.pop('temperature', 1.0), kw.pop('top_k', 0), kw.pop('top_p', 1.0)
+        ids = kw.pop('stream_ids', None)
+        level = max(int(kw.pop('controls_level', 0)),
+                    2 if nucleus_control(n_seqs, p) is not None else
+                    1 if sampling_controls(n_seqs, tau, k, self.model.q_levels) is not None else 0)
+        replay = noise is not None or sampler == 'torch'
+        fdim = cond.dim() - 2
+        num_cond = cond.shape[fdim]
+        L, Q = self.model.lookback, self.model.q_levels
+        if state is not None:
+            # (the checks of a call that continues `state`)
+            if not isinstance(state, GenState):
+                raise TypeError('Generator: state must be a GenState')
+            if state.n_seqs != n_seqs:
+                raise ValueError('Generator: state holds %d rows, the call has %d'
+                                 % (state.n_seqs, n_seqs))
+            if not replay and ids is None and bool((state.steps != state.steps[0]).any()):
+                raise ValueError('Generator: rows at differing step counts %s cannot continue '
+                                 'under sampler=\'philox\' (replayed noise can)'
+                                 % sorted(set(state.steps.tolist())))
+        with self.session(n_seqs, min(chunk_frames, num_cond), level=level, return_logp=logp,
+                          replay_noise=replay, **kw) as sess:
+            if state is not None:
+                sess.replace(list(range(n_seqs)), state)
+            ctl = dict(spk=spk, stream_ids=None if replay else ids)
+            if level >= 1:
+                ctl.update(temperature=tau, top_k=k)
+            if level >= 2:
+                ctl.update(top_p=p)
+            for f0 in range(0, num_cond, chunk_frames):
+                f1 = min(num_cond, f0 + chunk_frames)
+                q = None
+                if replay:
+                    q = (noise[f0 * L:f1 * L] if noise is not None else
+                         torch.empty((f1 - f0) * L, n_seqs, Q).exponential_(1))
+                res = sess.chunk(cond.narrow(fdim, f0, f1 - f0), noise=q, **ctl)
+                ctl = {}
+                if f1 == num_cond:
+                    self.last_state = sess.state()
+                yield res
+
+    def stream(self, n_seqs, cond, spk, chunk_frames, state=None, session=False, **kw):
         """Generates chunk_frames conditioning frames per call of __call__, each continuing from
         the state the previous one ended in, and yields every chunk's host float32
         (n_seqs, frames * lookback) block as it completes (with return_logp: (block, logp)).
@@ -1500,7 +1811,9 @@ class Generator(Runner):
         sampler='torch' draws each chunk's noise when the chunk starts -- the CPU generator's
         exponential_ stream does not depend on how it is cut -- so host memory is bounded by
         the chunk; a given `noise` is sliced.  The state after the last chunk is left in
-        self.last_state; `state` continues an earlier stream."""
+        self.last_state; `state` continues an earlier stream.
+        session=True runs the same chunks through one GenSession (no per-call set-up): the same
+        yields; self.last_state is then set once, after the last chunk."""
         chunk_frames = int(chunk_frames)
         if chunk_frames < 1:
             raise ValueError('Generator.stream: chunk_frames must be >= 1')
@@ -1508,6 +1821,9 @@ class Generator(Runner):
             if name in kw:
                 raise ValueError('Generator.stream: %s is not a stream argument' % name)
         cond = torch.as_tensor(np.asarray(cond) if not torch.is_tensor(cond) else cond)
+        if session:
+            yield from self._stream_session(n_seqs, cond, spk, chunk_frames, state, kw)
+            return
         fdim = cond.dim() - 2                      # the frame axis of (F, C) or (n_seqs, F, C)
         num_cond = cond.shape[fdim]
         L = self.model.lookback

@@ -108,6 +108,14 @@ _SIGS = {
                        _P, _P],
     'srnn_gen_state_fresh': [_P, _I, _P, _SZ, _P, _SZ, _P],
     'srnn_gen_state_bytes': [_P, _I],          # (returns size_t, not a status: see _Lib)
+    'srnn_gen_session_bytes': [_P, _I, _I, _I, _I, ctypes.POINTER(_SZ)],
+    'srnn_gen_session_open': [_P, _I, _I, _I, _U64, _I, _I, _P, _SZ, _P, ctypes.POINTER(_P)],
+    'srnn_gen_session_chunk': [_P, _P, _P],
+    'srnn_gen_session_sync': [_P],
+    'srnn_gen_session_state_get': [_P, _P, _SZ],
+    'srnn_gen_session_state_set_rows': [_P, _P, _I, _P, _SZ, _P],
+    'srnn_gen_session_stats': [_P, _P],
+    'srnn_gen_session_close': [_P],
     'srnn_sample_rows': [_P, _L, _I, _P, _U64, _I, _I, _P, _P, _P, _P, _P, _P],
     'srnn_persistent_flag_to_f32': [_P, _P],
     'srnn_persistent_flag_or_f32': [_P, _P],
@@ -150,6 +158,25 @@ class SrnnGenRows(ctypes.Structure):
     """The C ABI's SrnnGenRows (srnn_generate6): the rows' own Philox rows and step origins
     (device pointers or None)."""
     _fields_ = [('noise_row', _P), ('step0', _P)]
+
+
+GEN_SESSION_GRAPH, GEN_SESSION_PER_SAMPLE, GEN_SESSION_LOGP, GEN_SESSION_NOISE = 1, 2, 4, 8
+
+
+class SrnnGenChunk(ctypes.Structure):
+    """The C ABI's SrnnGenChunk (srnn_gen_session_chunk): one chunk's inputs and outputs, device
+    pointers or None but noise_row, a host int32 array."""
+    _fields_ = [('n_frames', _I), ('cond', _P), ('row_bias', _P), ('temperature', _P),
+                ('top_k', _P), ('top_p', _P), ('prefix', _P), ('prefix_cols', _I),
+                ('n_forced', _P), ('noise_row', _P), ('noise', _P), ('seq_out', _P),
+                ('logp_out', _P)]
+
+
+class SrnnGenSessionStats(ctypes.Structure):
+    """The C ABI's SrnnGenSessionStats (srnn_gen_session_stats)."""
+    _fields_ = [(n, ctypes.c_int64) for n in ('prepares', 'graphs_captured', 'graph_launches',
+                                              'eager_blocks', 'chunks', 'steps_min',
+                                              'steps_max')]
 
 
 EPI_AMAX, EPI_BLK, EPI_CSUM, EPI_LOGSOFTMAX = 1, 2, 4, 8

@@ -8,12 +8,15 @@ Modes, alternated in one process after a warm-up of each:
             to its own longest request (one-shot Generator.__call__, row_offset = first request)
   serve 32  Generator.serve(requests, 128, chunk_frames=32), stream ids = request positions
   serve 8   the same at chunk_frames=8
-Both forms run 128 rows per call, so request u is the same stream in all three: the outputs are
+  session 32 / session 8   Generator.serve(..., session=True): the same plans as the chunks of
+            one generation session (weights, workspace, records and graph kept between them)
+All forms run 128 rows per call, so request u is the same stream in every mode: the outputs are
 compared sample for sample.  Prints every round's wall time (a host clock around work that ends
 on the host), then per mode the median, useful samples per second (the requests' own frames x
 lookback / median) and the row-frames it ran; for serve also the plan's row-frames and calls.
-Every call re-folds the weights, carves a workspace and captures a graph (1.35-1.49
-ms per chunk), which is what a short chunk pays for its tighter packing.
+Every per-call chunk re-folds the weights, carves a workspace and captures a graph,
+which is what a short chunk pays for its tighter packing; a session's chunk does not.
+A fifth argument `per-call` leaves the session modes out (a tree without sessions).
 """
 import os
 import sys
@@ -63,11 +66,14 @@ def main():
                 out[r0 + b] = y[b, :r['cond'].shape[0] * L]
         return out
 
-    def served(rq, chunk):
-        return dict(gen.serve(rq, SLOTS, chunk, seed=5))
+    def served(rq, chunk, **how):
+        return dict(gen.serve(rq, SLOTS, chunk, seed=5, **how))
 
     modes = [('padded', padded)] + [('serve %d' % c, lambda rq, c=c: served(rq, c))
                                     for c in CHUNKS]
+    if not (len(sys.argv) > 5 and sys.argv[5] == 'per-call'):
+        modes += [('session %d' % c, lambda rq, c=c: served(rq, c, session=True))
+                  for c in CHUNKS]
     # warm-up on a short prefix of every request (graph capture, kernel attributes); the three
     # modes give the same streams
     short = [dict(r, cond=r['cond'][:4 + u % 5]) for u, r in enumerate(reqs[:2 * SLOTS])]
@@ -91,12 +97,12 @@ def main():
             if r == 0:
                 full = out if full is None else full
                 assert all(torch.equal(out[u], full[u]) for u in range(n_req)), name
-            print('round %d %-9s %.4f s' % (r, name, secs[name][-1]), flush=True)
+            print('round %d %-10s %.4f s' % (r, name, secs[name][-1]), flush=True)
     print('%d requests, %d..%d frames (%d useful frames), %d slots, bf16 D=1024, lookback %d; '
           'outputs of all modes equal' % (n_req, min(lengths), max(lengths), useful, SLOTS, L))
     for name, _ in modes:
         v = np.array(secs[name])
-        line = '%-9s median %.4f s (min %.4f max %.4f), %.0f useful samples/s' % (
+        line = '%-10s median %.4f s (min %.4f max %.4f), %.0f useful samples/s' % (
             name, np.median(v), v.min(), v.max(), useful * L / np.median(v))
         if name == 'padded':
             line += ', %d row-frames in %d calls' % (pad_rf, -(-n_req // SLOTS))
