@@ -129,7 +129,14 @@ int srnn_relu_bits(int dtype, const void* a, int64_t lda, int M, int N, unsigned
  * persistent sweep, the LDS-resident persistent sweep, or one srnn_gru_cell launch per step
  * (fp32 always; SRNN_GRU_XCD=0 / SRNN_GRU_SEQ=0 switch a sweep off).  srnn_gru_layer_plan
  * names it and gives the work bytes of either direction (0: pass no work buffer);
- * _plan_for is the same for a device of `ncu` CUs shared by `share` processes. */
+ * _plan_for is the same for a device of `ncu` CUs shared by `share` processes.
+ * Alignment.  Every operand is addressed by element (any ld / s, any base aligned to its
+ * element), with these exceptions, which a call that misses them refuses (non-zero return,
+ * nothing written): the XCD sweeps read W_hh / W_hh^T and their work buffer in 16-byte
+ * pieces (16-byte aligned pointers); the seq sweeps do so for W_hh / W_hh^T, h0_lp, and for
+ * the rows of out_lp and dgh_lp they hand over between steps (16-byte aligned pointers, ldo,
+ * so, ldd and sd multiples of 8 elements).  The step kernels take a slower path when h,
+ * dgh_next or a weight is not 16-byte aligned with a 16-byte row pitch. */
 enum SrnnGruBackend { SRNN_GRU_STEPS = 0, SRNN_GRU_SEQ = 1, SRNN_GRU_XCD = 2 };
 int srnn_gru_layer_plan(int dtype, int B, int D, int* backend, size_t* fwd_bytes,
                         size_t* bwd_bytes);

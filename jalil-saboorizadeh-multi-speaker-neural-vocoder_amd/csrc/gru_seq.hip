@@ -376,12 +376,18 @@ size_t gru_seq_area(int dtype, int B, int D, int ncu, int share) {
     return ((size_t)nm * 64 + 1) * sizeof(int);
 }
 
+static inline bool gseq_al16(const void* p) { return (uintptr_t)p % 16 == 0; }
+
 int gru_try_seq_fwd(const GruLayerFwd& p, hipStream_t s) {
     const size_t area = gru_seq_area(p.dtype, p.B, p.D, p.ncu, p.share);
     if (!area) return -1;
     SRNN_REQUIRE(p.work && p.work_bytes >= area, "gru_seq: workspace");
     SRNN_REQUIRE(p.h0_lp && p.out_lp && !p.hprev_lp,
                  "gru_seq: needs h0_lp and out_lp, writes no hprev_lp");
+    // W_hh and the h rows of every step arrive as 16-byte DMA pieces
+    SRNN_REQUIRE(gseq_al16(p.whh) && gseq_al16(p.h0_lp) && gseq_al16(p.out_lp) && p.ldo % 8 == 0 &&
+                     p.so % 8 == 0,
+                 "gru_seq: W_hh, h0_lp and out_lp must be 16-byte aligned, ldo and so multiples of 8");
     if (p.Fr <= 0) return 0;
     SRNN_CHECK_HIP(hipMemsetAsync(p.work, 0, area, s));
     const int nm = cdiv(p.B, gseq::BM);
@@ -408,6 +414,9 @@ int gru_try_seq_bwd(const GruLayerBwd& p, hipStream_t s) {
     SRNN_REQUIRE(p.work && p.work_bytes >= area, "gru_seq_bwd: workspace");
     SRNN_REQUIRE(p.dgh && p.dgh_lp && p.dgi && !p.dgi_lp && !p.bsum,
                  "gru_seq_bwd: writes dgh, dgh_lp and dgi, no dgi_lp / bsum");
+    // W_hh^T and the dgh rows of every step arrive as 16-byte DMA pieces
+    SRNN_REQUIRE(gseq_al16(p.whh_t) && gseq_al16(p.dgh_lp) && p.ldd % 8 == 0 && p.sd % 8 == 0,
+                 "gru_seq_bwd: W_hh^T and dgh_lp must be 16-byte aligned, ldd and sd multiples of 8");
     if (p.Fr <= 0) return 0;
     SRNN_CHECK_HIP(hipMemsetAsync(p.work, 0, area, s));
     const int nm = cdiv(p.B, gseqb::BM);

@@ -1109,6 +1109,9 @@ int gru_try_xcd_fwd(const GruLayerFwd& p, hipStream_t s) {
     if (!need) return -1;
     SRNN_REQUIRE(p.work && p.work_bytes >= need, "gru_xcd: workspace %zu < %zu", p.work_bytes,
                  need);
+    // W_hh rows are read as 16-byte pieces, the granules as 16-byte buffer loads
+    SRNN_REQUIRE((uintptr_t)p.whh % 16 == 0 && (uintptr_t)p.work % 16 == 0,
+                 "gru_xcd: W_hh and work must be 16-byte aligned");
     if (Fr <= 0) return 0;
     const int lr = gx_launch_rows(D, p.ncu / p.share);
     if (B > lr) {     // rows are independent: consecutive launches over row chunks
@@ -1176,6 +1179,8 @@ int gru_try_xcd_bwd(const GruLayerBwd& p, hipStream_t s) {
     SRNN_REQUIRE(p.work && p.work_bytes >= need, "gru_xcd_bwd: workspace %zu < %zu", p.work_bytes,
                  need);
     SRNN_REQUIRE(p.dgh_lp, "gru_xcd_bwd: dgh_lp is required");
+    SRNN_REQUIRE((uintptr_t)p.whh_t % 16 == 0 && (uintptr_t)p.work % 16 == 0,
+                 "gru_xcd_bwd: W_hh^T and work must be 16-byte aligned");
     if (Fr <= 0) return 0;
     const int lr = gx_launch_rows(D, p.ncu / p.share);
     if (B > lr) {     // rows are independent: consecutive launches over row chunks
@@ -1268,9 +1273,10 @@ int gru_try_xcd_bwd(const GruLayerBwd& p, hipStream_t s) {
           gru_xcd_bwd_kernel<12, true, 4>}}};
     const BwdK k = ks[full ? 1 : 0][ui][mi];
     SRNN_REQUIRE(k, "gru_xcd_bwd: no kernel for D=%d", D);
-    // (this form's LDS fits the default limit: not raised)
-    return srnn_persist_launch((const void*)k, dim3(a.G * a.P), gx::NTHR, lds, 0, &a,
-                               "gru_xcd_bwd", s);
+    // (this form's LDS fits the default 64 KiB limit up to MT = 2; MT = 4 adds 40 KiB of
+    //  per-tile state slots and needs the limit raised)
+    return srnn_persist_launch((const void*)k, dim3(a.G * a.P), gx::NTHR, lds,
+                               lds > 64 * 1024 ? 160 * 1024 : 0, &a, "gru_xcd_bwd", s);
 }
 
 // nonzero if the previous XCD sweep on `work` gave up a hand-off (synchronises)
