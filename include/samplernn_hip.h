@@ -337,6 +337,40 @@ int srnn_mlp_dtab4(int dtype, const void* da, int64_t ldda, const int64_t* x, in
  * only while they have no static LDS (checked from the compiled kernels' attributes; 0 sends
  * srnn_mlp_dtab4 to the exact form).  Diagnostic; needs a device.                        */
 int srnn_dtab_packed_ok(void);
+/* The routes of srnn_mlp_dtab4 and of srnn_mlp_l1 / srnn_mlp_l1_bits (csrc/mlp_plan.hpp): each
+ * operation has one plan, a pure function of the call's shapes, strides, pointer alignments
+ * and switches, and these entries report it.  Every route of one operation writes the same
+ * bits.  Diagnostic; they replace no reference interface and launch nothing.
+ * dTab: packed (bf16 in and out, FS0 = 16, Q = 256, D % 8 == 0 and >= 768, ldda % 8 == 0;
+ * SRNN_DTAB_PACK=0 switches it off), direct and posws (the position-major form, FS0 = 16:
+ * straight into dtab_out when D >= 765, else through the int64 workspace; SRNN_DTAB_POS=0),
+ * generic (any FS0, `cw` columns per workgroup), empty (no rows: zeros).
+ * srnn_mlp_dtab_plan_for writes the route, and for it: cw (generic: 4 / 2 / 1), pd (packed: the
+ * prefetch depth 1 / 2 / 4; SRNN_DTAB_PD, default by B), x8 (packed: the sample windows are
+ * staged as bytes in work; needs room there, SRNN_DTAB_X8=0), use_blk (packed: blk is read;
+ * SRNN_DTAB_BLK=0), colsum (1: the route writes colsum and sets *colsum_done when given one)
+ * and need_bytes, the work bytes the call requires.  have_amax / have_blk: amax_in / blk would
+ * be non-NULL; packed_ok: what srnn_dtab_packed_ok() answers on the device in question.
+ * srnn_mlp_dtab_plan is the same with packed_ok taken from the current device.             */
+enum SrnnDtabRoute { SRNN_DTAB_EMPTY = 0, SRNN_DTAB_GENERIC = 1, SRNN_DTAB_POSWS = 2,
+                     SRNN_DTAB_DIRECT = 3, SRNN_DTAB_PACKED = 4 };
+int srnn_mlp_dtab_plan_for(int dtype, int out_dtype, int B, int Tlen, int D, int FS0, int Q,
+                           int64_t ldda, int have_amax, int have_blk, size_t work_bytes,
+                           int packed_ok, int* route, int* cw, int* pd, int* x8, int* use_blk,
+                           int* colsum, size_t* need_bytes);
+int srnn_mlp_dtab_plan(int dtype, int out_dtype, int B, int Tlen, int D, int FS0, int Q,
+                       int64_t ldda, int have_amax, int have_blk, size_t work_bytes, int* route,
+                       int* cw, int* pd, int* x8, int* use_blk, int* colsum, size_t* need_bytes);
+/* L1 gather: lds (bf16 table and upper, FS0 = 16, Q = 256, D % 16 == 0, Tlen <= 2029; the
+ * table slice stays in LDS; SRNN_L1_LDS=0 switches it off), xcd (D % 128 == 0) -- both need
+ * >= 4096 rows, 16-byte aligned tab / upper / out and 16-byte row pitches, and no device
+ * `base` offset (generation's single rows) -- else generic.  tab / upper / out are looked at
+ * as addresses only, never read.  *bits_pass = 1: with have_bits the mask bits come from a
+ * separate srnn_relu_bits pass over out (every route but lds, which writes them itself).   */
+enum SrnnL1Route { SRNN_L1_GENERIC = 0, SRNN_L1_XCD = 1, SRNN_L1_LDS = 2 };
+int srnn_mlp_l1_plan_for(int dtype, int upper_dtype, int B, int Tlen, int D, int FS0, int Q,
+                         const void* tab, const void* upper, int64_t ldu, const void* out,
+                         int64_t ldo, int have_base, int have_bits, int* route, int* bits_pass);
 /* Number of GEMMs srnn_gemm / srnn_gemm_bits handed to hipBLASLt so far in this process:
  * large plain bf16 problems (alpha, per-column bias, ReLU, beta 0, no mask; M N >= 4 Mi,
  * 2 M N K >= 2^33) run as the ROCm library GEMM (SRNN_BLASLT=0: the library's own gemm3

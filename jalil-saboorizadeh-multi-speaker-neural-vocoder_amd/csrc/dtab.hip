@@ -17,9 +17,9 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "mlp_plan.hpp"
 #include "samplernn_hip_internal.hpp"
 
-#define DTAB_NT 1024
 #define DTAB_SCALE 1099511627776.0          // 2^40
 
 // round(g * 2^40) as int64 in four instructions: the f64 fma against 1.5 * 2^52 leaves
@@ -633,40 +633,30 @@ __global__ void dtab_fx_convert_kernel(const unsigned long long* __restrict__ fx
     out[i] = from_f<TO>((float)((double)(long long)fx[i] * (1.0 / DTAB_SCALE)));
 }
 
+// ---------------------------------------------------------------------------------
+// Host side.  srnn_mlp_dtab4 fills a DtabProblem, dtab_plan (mlp_plan.cpp) names the route,
+// and one launcher per route below sizes its grid and launches.
+static_assert(sizeof(DtabStat) == DTAB_STAT_BYTES, "mlp_plan.hpp lays out the work area with it");
+
+static unsigned long long* dtab_fx(const DtabProblem& p) { return (unsigned long long*)p.work; }
+
 template <typename T, int CW, int FSC>
-static int launch_dtab(const void* da, int64_t ldda, const int64_t* x, int64_t ldx, int xoff,
-                       int B, int Tlen, unsigned long long* fx, int D, int FS0, int Q,
-                       hipStream_t s) {
-    const int acc_bytes = Q * FS0 * CW * 8;
-    const int W = Tlen + FS0 - 1;
-    const int nb_cap = std::max(1, (160 * 1024 - acc_bytes) / W);
-    const int nslices = cdiv(D, CW);
+static int launch_dtab(const DtabProblem& p, hipStream_t s) {
+    const int acc_bytes = p.Q * p.FS0 * CW * 8;
+    const int W = p.Tlen + p.FS0 - 1;
+    const int nb_cap = std::max(1, (MLP_LDS_MAX - acc_bytes) / W);
+    const int nslices = cdiv(p.D, CW);
     const int nblk = std::max(1, 1024 / nslices);
-    int nb = std::min(B, std::max(cdiv(B, nblk), 1));
+    int nb = std::min(p.B, std::max(cdiv(p.B, nblk), 1));
     nb = std::min(nb, nb_cap);
     const int lds = acc_bytes + ((nb * W + 15) / 16) * 16;
-    static bool attr = false;
-    if (!attr) {
-        SRNN_CHECK_HIP(hipFuncSetAttribute((const void*)dtab_fx_kernel<T, CW, FSC>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr = true;
-    }
-    const int nrb = cdiv(B, nb);
-    dim3 grid(nslices * nrb);
-    hipLaunchKernelGGL((dtab_fx_kernel<T, CW, FSC>), grid, dim3(DTAB_NT), lds, s, (const T*)da, ldda, x,
-                       ldx, xoff, Tlen, B, nb, nrb, fx, D, FS0, Q);
+    auto k = dtab_fx_kernel<T, CW, FSC>;
+    if (const int rc = srnn_raise_lds((const void*)k, MLP_LDS_MAX)) return rc;
+    const int nrb = cdiv(p.B, nb);
+    hipLaunchKernelGGL(k, dim3(nslices * nrb), dim3(DTAB_NT), lds, s, (const T*)p.da, p.ldda, p.x,
+                       p.ldx, p.xoff, p.Tlen, p.B, nb, nrb, dtab_fx(p), p.D, p.FS0, p.Q);
     SRNN_LAUNCH_CHECK();
     return 0;
-}
-
-static bool getenv_off(const char* name) {
-    const char* e = getenv(name);
-    return e && e[0] == '0';
-}
-
-static int pos_lds_bytes(int Q, int Tlen) {
-    const int W = Tlen + 15, WPB = (W + 31) & ~15;
-    return Q * 16 * 4 * 8 + 4 * 16 * 8 + (DTAB_NT / 64) * WPB;
 }
 
 // The packed kernel builds its LDS bin addresses without a base: valid only while it has no
@@ -689,160 +679,120 @@ static bool pk_static_lds_ok() {
 
 extern "C" int srnn_dtab_packed_ok(void) { return pk_static_lds_ok() ? 1 : 0; }
 
-static int pk_lds_bytes(int Q, int Tlen) {
-    const int W = Tlen + 15, WPB = (W + 31) & ~15;
-    return Q * 2 * 16 * 8 + 4 * 16 * 8 + 16 + (DTAB_NT / 64) * 2 * WPB;
-}
-
+// One position-major launch over row blocks of nb batch rows.  gate: the packed form's
+// statistics, when this is the exact form behind it.
 template <typename T, typename TO, bool DIRECT>
-static int launch_pos(const void* da, int64_t ldda, const int64_t* x, int64_t ldx, int xoff, int B,
-                      int Tlen, unsigned long long* fx, void* out, float* colsum, int D, int Q,
-                      int nb, int nrb, hipStream_t s, const DtabStat* gate = nullptr,
-                      const unsigned* gate_amax = nullptr) {
-    const int lds = pos_lds_bytes(Q, Tlen);
-    const int nslices = cdiv(D, 4);
+static int launch_pos(const DtabProblem& p, int nb, int nrb, hipStream_t s,
+                      const DtabStat* gate = nullptr) {
     auto k = dtab_pos_kernel<T, TO, DIRECT>;
-    static bool attr = false;
-    if (!attr) {
-        SRNN_CHECK_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           160 * 1024));
-        attr = true;
-    }
-    hipLaunchKernelGGL(k, dim3(nslices * nrb), dim3(DTAB_NT), lds, s, (const T*)da, ldda, x, ldx,
-                       xoff, Tlen, B, nb, nrb, fx, (TO*)out, colsum, D, Q, gate, gate_amax);
+    if (const int rc = srnn_raise_lds((const void*)k, MLP_LDS_MAX)) return rc;
+    hipLaunchKernelGGL(k, dim3(cdiv(p.D, 4) * nrb), dim3(DTAB_NT), pos_lds_bytes(p.Q, p.Tlen), s,
+                       (const T*)p.da, p.ldda, p.x, p.ldx, p.xoff, p.Tlen, p.B, nb, nrb,
+                       gate ? nullptr : dtab_fx(p), (TO*)p.dtab_out, DIRECT ? p.colsum : nullptr,
+                       p.D, p.Q, gate, gate ? p.amax_in : nullptr);
     SRNN_LAUNCH_CHECK();
     return 0;
 }
 
-// position-major path (FS0 == 16); returns 1 if it wrote dtab_out directly
+// packed: statistics, the packed scatter, and the exact form gated behind it
+static int dtab_run_packed(const DtabProblem& p, const DtabPlan& pl, hipStream_t s) {
+    DtabStat* st = (DtabStat*)p.work;
+    SRNN_CHECK_HIP(hipMemsetAsync(st, 0, sizeof(DtabStat), s));
+    // the windows as bytes for the packed scatter (else it reads the int64 x)
+    const int wp8 = dtab_wp8(p.Tlen);
+    unsigned char* x8 = pl.x8 ? (unsigned char*)p.work + DTAB_X8_OFF : nullptr;
+    const bf16* da = (const bf16*)p.da;
+    hipLaunchKernelGGL(dtab_prep_kernel<bf16>, dim3(pl.nb_da + p.B), dim3(256), 0, s, da, p.ldda,
+                       (int64_t)p.B * p.Tlen, p.D, p.x, p.ldx, p.xoff, p.Tlen + 15, p.B, pl.nb_da,
+                       st, x8, wp8);
+    SRNN_LAUNCH_CHECK();
+    auto pk = pl.use_blk ? dtab_pk_kernel<bf16, 4, true>
+            : pl.pd == 1 ? dtab_pk_kernel<bf16, 1>
+            : pl.pd == 2 ? dtab_pk_kernel<bf16, 2> : dtab_pk_kernel<bf16, 4>;
+    if (const int rc = srnn_raise_lds((const void*)pk, MLP_LDS_MAX)) return rc;
+    hipLaunchKernelGGL(pk, dim3(cdiv(p.D, 4)), dim3(DTAB_NT), pk_lds_bytes(p.Q, p.Tlen), s, da,
+                       p.ldda, p.x, p.ldx, p.xoff, p.Tlen, p.B, st, p.amax_in, (bf16*)p.dtab_out,
+                       p.colsum, p.D, p.Q, (const bf16*)p.blk, x8, wp8);
+    SRNN_LAUNCH_CHECK();
+    // all of the exact form's workgroups return at once unless the packed form declined (a
+    // skewed sample histogram)
+    return launch_pos<bf16, bf16, true>(p, p.B, 1, s, st);
+}
+
+// direct: every workgroup takes all rows of its 4 columns and stores the output itself
+static int dtab_run_direct(const DtabProblem& p, hipStream_t s) {
+    const bool fo = p.out_dtype == SRNN_F32;
+    if (p.dtype == SRNN_F32)
+        return fo ? launch_pos<float, float, true>(p, p.B, 1, s)
+                  : launch_pos<float, bf16, true>(p, p.B, 1, s);
+    return fo ? launch_pos<bf16, float, true>(p, p.B, 1, s)
+              : launch_pos<bf16, bf16, true>(p, p.B, 1, s);
+}
+
+// posws: row blocks that fill the device, summed into the int64 workspace
+static int dtab_run_posws(const DtabProblem& p, hipStream_t s) {
+    const int nblk = std::max(1, 1024 / cdiv(p.D, 4));
+    const int nb = std::max(1, cdiv(p.B, nblk)), nrb = cdiv(p.B, nb);
+    return p.dtype == SRNN_F32 ? launch_pos<float, float, false>(p, nb, nrb, s)
+                               : launch_pos<bf16, float, false>(p, nb, nrb, s);
+}
+
 template <typename T>
-static int dtab_pos(const void* da, int64_t ldda, const int64_t* x, int64_t ldx, int xoff, int B,
-                    int Tlen, unsigned long long* fx, void* out, int out_dtype, float* colsum,
-                    int D, int Q, bool* direct, hipStream_t s) {
-    const int nslices = cdiv(D, 4);
-    if (nslices >= 192) {          // every workgroup takes all rows of its 4 columns
-        *direct = true;
-        return out_dtype == SRNN_F32
-                   ? launch_pos<T, float, true>(da, ldda, x, ldx, xoff, B, Tlen, fx, out, colsum, D, Q, B, 1, s)
-                   : launch_pos<T, bf16, true>(da, ldda, x, ldx, xoff, B, Tlen, fx, out, colsum, D, Q, B, 1, s);
-    }
-    *direct = false;
-    const int nblk = std::max(1, 1024 / nslices);
-    const int nb = std::max(1, cdiv(B, nblk));
-    return launch_pos<T, float, false>(da, ldda, x, ldx, xoff, B, Tlen, fx, out, nullptr, D, Q, nb,
-                                       cdiv(B, nb), s);
+static int dtab_run_generic_as(const DtabProblem& p, int cw, hipStream_t s) {
+    if (cw == 4 && p.FS0 == 16) return launch_dtab<T, 4, 16>(p, s);
+    return cw == 4 ? launch_dtab<T, 4, 0>(p, s)
+         : cw == 2 ? launch_dtab<T, 2, 0>(p, s) : launch_dtab<T, 1, 0>(p, s);
+}
+
+static int dtab_run_generic(const DtabProblem& p, const DtabPlan& pl, hipStream_t s) {
+    SRNN_REQUIRE(pl.cw, "dtab: FS0 too large");
+    return p.dtype == SRNN_F32 ? dtab_run_generic_as<float>(p, pl.cw, s)
+                               : dtab_run_generic_as<bf16>(p, pl.cw, s);
 }
 
 // dtab_out (Q, FS0, D) in out_dtype; work: >= Q*FS0*D*8 bytes of device scratch.
 // colsum (optional, (FS0 * D) fp32): sum over batch rows of da rows t = j (mod FS0) at
-// [j * D + c]; *colsum_done (host) = 1 when it was written (the direct position-major path)
+// [j * D + c]; *colsum_done (host) = 1 when it was written (the plan's routes that do)
 extern "C" int srnn_mlp_dtab4(int dtype, const void* da, int64_t ldda, const int64_t* x,
                               int64_t ldx, int xoff, int B, int Tlen, void* dtab_out,
                               int out_dtype, int D, int FS0, int Q, void* work, size_t work_bytes,
                               float* colsum, int* colsum_done, const unsigned* amax_in,
                               const void* blk, void* stream) {
+    DtabProblem p;
+    p.dtype = dtype; p.out_dtype = out_dtype;
+    p.B = B; p.Tlen = Tlen; p.D = D; p.FS0 = FS0; p.Q = Q;
+    p.da = da; p.ldda = ldda; p.x = x; p.ldx = ldx; p.xoff = xoff; p.dtab_out = dtab_out;
+    p.work = work; p.work_bytes = work_bytes;
+    p.colsum = colsum; p.amax_in = amax_in; p.blk = blk;
     SRNN_REQUIRE(Q <= 256, "dtab: q_levels must be <= 256 (byte indices)");
-    const int64_t n = (int64_t)Q * FS0 * D;
-    SRNN_REQUIRE(work && work_bytes >= (size_t)n * 8, "dtab: workspace too small");
+    SRNN_REQUIRE(work && work_bytes >= dtab_work_bytes(p), "dtab: workspace too small");
+    const DtabPlan pl = dtab_plan(p, pk_static_lds_ok(), DtabSwitches::read());
     hipStream_t s = (hipStream_t)stream;
-    unsigned long long* fx = (unsigned long long*)work;
     if (colsum_done) *colsum_done = 0;
-    if (dtype == SRNN_BF16 && out_dtype == SRNN_BF16 && FS0 == 16 && Q == 256 && D % 8 == 0 &&
-        ldda % 8 == 0 &&
-        cdiv(D, 4) >= 192 && pk_lds_bytes(Q, Tlen) <= 160 * 1024 &&
-        // the packed kernel writes nothing when the histogram is too skewed for its scale and
-        // leaves dTab to the gated exact form: take it only where that form fits too
-        pos_lds_bytes(Q, Tlen) <= 160 * 1024 && (int64_t)B * Tlen > 0 &&
-        work_bytes >= sizeof(DtabStat) && !getenv_off("SRNN_DTAB_PACK") && pk_static_lds_ok()) {
-        DtabStat* st = (DtabStat*)work;
-        SRNN_CHECK_HIP(hipMemsetAsync(st, 0, sizeof(DtabStat), s));
-        const int64_t nrows = (int64_t)B * Tlen;
-        // amax_in: max |da| already measured by the GEMM that wrote da (SrnnGemmEpilogue.amax):
-        // the prep pass only counts the sample values
-        const int nb_da = amax_in ? 0 : (int)std::min<int64_t>(1024, std::max<int64_t>(1, nrows / 64));
-        const int W = Tlen + 15;
-        // the windows as bytes for the packed scatter (SRNN_DTAB_X8=0: it reads the int64 x)
-        const int wp8 = (W + 15) & ~15;
-        const size_t x8off = (sizeof(DtabStat) + 255) & ~(size_t)255;
-        unsigned char* x8 = nullptr;
-        if (work_bytes >= x8off + (size_t)B * wp8 && !getenv_off("SRNN_DTAB_X8"))
-            x8 = (unsigned char*)work + x8off;
-        hipLaunchKernelGGL(dtab_prep_kernel<bf16>, dim3(nb_da + B), dim3(256), 0, s,
-                           (const bf16*)da, ldda, nrows, D, x, ldx, xoff, W, B, nb_da, st, x8, wp8);
-        SRNN_LAUNCH_CHECK();
-        static bool attr = false;
-        if (!attr) {
-            for (const void* k : {(const void*)dtab_pk_kernel<bf16, 1>,
-                                  (const void*)dtab_pk_kernel<bf16, 2>,
-                                  (const void*)dtab_pk_kernel<bf16, 4>,
-                                  (const void*)dtab_pk_kernel<bf16, 4, true>})
-                SRNN_CHECK_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   160 * 1024));
-            attr = true;
-        }
-        // da prefetch depth, in batches (SRNN_DTAB_PD = 1 / 2 / 4 overrides): measured per B on
-        // one box (profiles/r05_dtab_rowmajor_perm_ab.txt) -- two ahead up to B = 256, one ahead
-        // at B = 512 (1.20 vs 1.29 / 1.32 ms; deeper prefetch there is slower, not faster);
-        // blk: the column-blocked copy of da (SRNN_DTAB_BLK=0 reads the row-major da)
-        const char* pde = getenv("SRNN_DTAB_PD");
-        const bool useblk = blk && !getenv_off("SRNN_DTAB_BLK");
-        const int pd = (pde && pde[0]) ? atoi(pde) : (B >= 384 ? 1 : 2);
-        auto pk = useblk ? dtab_pk_kernel<bf16, 4, true>
-                : pd == 1 ? dtab_pk_kernel<bf16, 1>
-                : pd == 2 ? dtab_pk_kernel<bf16, 2> : dtab_pk_kernel<bf16, 4>;
-        hipLaunchKernelGGL(pk, dim3(cdiv(D, 4)), dim3(DTAB_NT),
-                           pk_lds_bytes(Q, Tlen), s, (const bf16*)da, ldda, x, ldx, xoff, Tlen, B,
-                           st, amax_in, (bf16*)dtab_out, colsum, D, Q, (const bf16*)blk, x8,
-                           wp8);
-        SRNN_LAUNCH_CHECK();
-        // the exact form behind it, gated on the same statistics: all of its workgroups
-        // return at once unless the packed form declined (a skewed sample histogram)
-        const int rc = launch_pos<bf16, bf16, true>(da, ldda, x, ldx, xoff, B, Tlen, nullptr,
-                                                    dtab_out, colsum, D, Q, B, 1, s, st, amax_in);
-        if (rc) return rc;
-        if (colsum && colsum_done) *colsum_done = 1;
-        return 0;
+    // packed and direct store dtab_out themselves; the others (empty: nothing) sum into the
+    // zeroed int64 workspace, which one pass then converts
+    const bool via_fx = pl.route != SRNN_DTAB_PACKED && pl.route != SRNN_DTAB_DIRECT;
+    const int64_t n = (int64_t)Q * FS0 * D;
+    if (via_fx) SRNN_CHECK_HIP(hipMemsetAsync(work, 0, (size_t)n * 8, s));
+    int rc = 0;
+    switch (pl.route) {
+    case SRNN_DTAB_PACKED: rc = dtab_run_packed(p, pl, s); break;
+    case SRNN_DTAB_DIRECT: rc = dtab_run_direct(p, s); break;
+    case SRNN_DTAB_POSWS: rc = dtab_run_posws(p, s); break;
+    case SRNN_DTAB_GENERIC: rc = dtab_run_generic(p, pl, s); break;
+    default: break;
     }
-    if (FS0 == 16 && pos_lds_bytes(Q, Tlen) <= 160 * 1024 && (int64_t)B * Tlen > 0 &&
-        !getenv_off("SRNN_DTAB_POS")) {
-        bool direct = false;
-        if (cdiv(D, 4) < 192) SRNN_CHECK_HIP(hipMemsetAsync(fx, 0, (size_t)n * 8, s));
-        const int rc = dtype == SRNN_F32
-            ? dtab_pos<float>(da, ldda, x, ldx, xoff, B, Tlen, fx, dtab_out, out_dtype, colsum, D, Q, &direct, s)
-            : dtab_pos<bf16>(da, ldda, x, ldx, xoff, B, Tlen, fx, dtab_out, out_dtype, colsum, D, Q, &direct, s);
-        if (rc) return rc;
-        if (direct) {
-            if (colsum && colsum_done) *colsum_done = 1;
-            return 0;
-        }
-        goto convert;
-    }
-    SRNN_CHECK_HIP(hipMemsetAsync(fx, 0, (size_t)n * 8, s));
-    if ((int64_t)B * Tlen > 0) {
-        const int W = Tlen + FS0 - 1;
-        int cw = 4;
-        while (cw > 1 && (Q * FS0 * cw * 8 + W > 160 * 1024 || FS0 * cw > DTAB_NT)) cw /= 2;
-        SRNN_REQUIRE(Q * FS0 * cw * 8 + W <= 160 * 1024 && FS0 * cw <= DTAB_NT,
-                     "dtab: FS0 too large");
-        int rc;
-#define DTAB_GO(TT, CWV, FSV) launch_dtab<TT, CWV, FSV>(da, ldda, x, ldx, xoff, B, Tlen, fx, D, FS0, Q, s)
-        if (dtype == SRNN_F32)
-            rc = (cw == 4 && FS0 == 16) ? DTAB_GO(float, 4, 16)
-               : cw == 4 ? DTAB_GO(float, 4, 0) : cw == 2 ? DTAB_GO(float, 2, 0) : DTAB_GO(float, 1, 0);
+    if (rc) return rc;
+    if (via_fx) {
+        if (out_dtype == SRNN_F32)
+            hipLaunchKernelGGL(dtab_fx_convert_kernel<float>, dim3(cdiv(n, 256)), dim3(256), 0, s,
+                               dtab_fx(p), (float*)dtab_out, n);
         else
-            rc = (cw == 4 && FS0 == 16) ? DTAB_GO(bf16, 4, 16)
-               : cw == 4 ? DTAB_GO(bf16, 4, 0) : cw == 2 ? DTAB_GO(bf16, 2, 0) : DTAB_GO(bf16, 1, 0);
-#undef DTAB_GO
-        if (rc) return rc;
+            hipLaunchKernelGGL(dtab_fx_convert_kernel<bf16>, dim3(cdiv(n, 256)), dim3(256), 0, s,
+                               dtab_fx(p), (bf16*)dtab_out, n);
+        SRNN_LAUNCH_CHECK();
     }
-convert:
-    if (out_dtype == SRNN_F32)
-        hipLaunchKernelGGL(dtab_fx_convert_kernel<float>, dim3(cdiv(n, 256)), dim3(256), 0, s, fx,
-                           (float*)dtab_out, n);
-    else
-        hipLaunchKernelGGL(dtab_fx_convert_kernel<bf16>, dim3(cdiv(n, 256)), dim3(256), 0, s, fx,
-                           (bf16*)dtab_out, n);
-    SRNN_LAUNCH_CHECK();
+    if (colsum_done) *colsum_done = colsum && pl.colsum;
     return 0;
 }
 

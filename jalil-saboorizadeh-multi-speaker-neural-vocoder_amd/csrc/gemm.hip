@@ -319,20 +319,15 @@ static int launch_types(const GemmArgs& g, bool kca, bool kcb, int batch, int ti
     return launch_layout<T, TO, false, false>(g, batch, tile, s);
 }
 
-static bool env_on(const char* name) {
-    const char* e = getenv(name);
-    return !(e && e[0] == '0');
-}
-
 static bool g_use_gemm2() {
     static int v = -1;
-    if (v < 0) v = env_on("SRNN_GEMM2") ? 1 : 0;
+    if (v < 0) v = !env_off("SRNN_GEMM2") ? 1 : 0;
     return v == 1;
 }
 
 static bool g_use_gemm3() {
     static int v = -1;
-    if (v < 0) v = env_on("SRNN_GEMM3") ? 1 : 0;
+    if (v < 0) v = !env_off("SRNN_GEMM3") ? 1 : 0;
     return v == 1;
 }
 

@@ -14,6 +14,7 @@
 // supplied (bit-replay of the reference's RNG) or from a counter-based Philox4x32-10.
 #include <algorithm>
 
+#include "mlp_plan.hpp"
 #include "samplernn_hip_internal.hpp"
 #include "sampler.hpp"
 
@@ -140,7 +141,6 @@ __global__ __launch_bounds__(256) void mlp_l1_xcd_kernel(const T* __restrict__ t
 // (tools/dot2_probe).  The summation order (upper, then taps 0..15) is mlp_l1_xcd_kernel's,
 // so both produce identical bits.
 typedef __bf16 l1_bf16x2 __attribute__((ext_vector_type(2)));
-constexpr int L1L_NT = 1024;
 
 __device__ __forceinline__ void l1l_add8(const uint4 v, float (&a)[8], l1_bf16x2 lo1,
                                          l1_bf16x2 hi1) {
@@ -291,60 +291,63 @@ __global__ __launch_bounds__(L1L_NT, 1) void mlp_l1_lds_kernel(
     }
 }
 
+// ---- host side: the entries fill an L1Problem, l1_plan (mlp_plan.cpp) names the route
+static int l1_run_lds(const L1Problem& p, const L1Plan& pl, hipStream_t s) {
+    auto kern = pl.rpt == 2 ? mlp_l1_lds_kernel<2> : mlp_l1_lds_kernel<4>;
+    if (const int rc = srnn_raise_lds((const void*)kern, MLP_LDS_MAX)) return rc;
+    hipLaunchKernelGGL(kern, dim3(p.D / 16 * pl.nrc2), dim3(L1L_NT), l1_lds_bytes(p.Tlen, p.FS0), s,
+                       (const bf16*)p.tab, p.x, p.ldx, p.xoff, p.B, p.Tlen, pl.bpc,
+                       (const bf16*)p.upper, p.ldu, (bf16*)p.out, p.ldo, p.D, p.bits, p.ldb);
+    SRNN_LAUNCH_CHECK();
+    return 0;
+}
+
+// the XCD-sliced and the generic gather, for a table / upper dtype pair
 template <typename T, typename TU>
-static int mlp_l1_launch(const T* tab, const int64_t* x, int64_t ldx, int xoff, const int* base,
-                         int B, int Tlen, const TU* upper, int64_t ldu, T* out, int64_t ldo,
-                         int D, int FS0, int Q, hipStream_t s, unsigned short* bits = nullptr,
-                         int64_t ldb = 0) {
-    const int64_t nrows = (int64_t)B * Tlen;
-    const int ue = (int)sizeof(TU);
-    if constexpr (sizeof(T) == 2 && sizeof(TU) == 2) {
-        const int W = Tlen + FS0 - 1, WP = (W + 4 + 15) & ~15;
-        const int ncg = D / 16;
-        const int lds = 16 * 256 * 32 + 2 * WP;
-        if (!base && FS0 == 16 && Q == 256 && D % 16 == 0 && ncg <= 256 && lds <= 160 * 1024 &&
-            Tlen <= 4 * (L1L_NT / 2) && WP <= 2 * L1L_NT &&
-            nrows >= 4096 && ldu % 8 == 0 && (uintptr_t)upper % 16 == 0 && ldo % 8 == 0 &&
-            (uintptr_t)out % 16 == 0 && (uintptr_t)tab % 16 == 0 && env_flag("SRNN_L1_LDS", 1)) {
-            const int nrc = std::max(1, std::min(B, 256 / ncg));
-            const int bpc = (B + nrc - 1) / nrc;
-            const int nrc2 = (B + bpc - 1) / bpc;
-            const int nrt = (Tlen + L1L_NT / 2 - 1) / (L1L_NT / 2);
-            auto kern = nrt <= 2 ? mlp_l1_lds_kernel<2> : mlp_l1_lds_kernel<4>;
-            static bool attr[2] = {false, false};
-            if (!attr[nrt > 2]) {
-                SRNN_CHECK_HIP(hipFuncSetAttribute((const void*)kern,
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   160 * 1024));
-                attr[nrt > 2] = true;
-            }
-            hipLaunchKernelGGL(kern, dim3(ncg * nrc2), dim3(L1L_NT), lds, s,
-                               (const bf16*)tab, x, ldx, xoff, B, Tlen, bpc, (const bf16*)upper,
-                               ldu, (bf16*)out, ldo, D, bits, ldb);
-            SRNN_LAUNCH_CHECK();
-            return 0;
-        }
-    }
-    if (!base && D % 128 == 0 && nrows >= 4096 && (ldu * ue) % 16 == 0 &&
-        (uintptr_t)upper % 16 == 0 && (ldo * (int)sizeof(T)) % 16 == 0 &&
-        (uintptr_t)out % 16 == 0 && (uintptr_t)tab % 16 == 0) {
-        const int nslices = D / 128;
+static int l1_run_gather(const L1Problem& p, const L1Plan& pl, hipStream_t s) {
+    const int64_t nrows = (int64_t)p.B * p.Tlen;
+    const T* tab = (const T*)p.tab;
+    const TU* upper = (const TU*)p.upper;
+    T* out = (T*)p.out;
+    if (pl.route == SRNN_L1_XCD) {
+        const int nslices = p.D / 128;
         const int rpb = 64;
         const int64_t nblk = (nrows + rpb - 1) / rpb * nslices;
         SRNN_REQUIRE(nblk < (1ll << 31), "mlp_l1: too many rows");
         hipLaunchKernelGGL((mlp_l1_xcd_kernel<T, TU>), dim3((unsigned)nblk), dim3(256), 0, s, tab,
-                           x, ldx, xoff, Tlen, nrows, rpb, nslices, upper, ldu, out, ldo, D, FS0, Q);
+                           p.x, p.ldx, p.xoff, p.Tlen, nrows, rpb, nslices, upper, p.ldu, out,
+                           p.ldo, p.D, p.FS0, p.Q);
     } else {
-        dim3 grid(cdiv(D, 256 * 4), nrows);
-        hipLaunchKernelGGL((mlp_l1_kernel<T, TU, 4>), grid, dim3(256), 0, s, tab, x, ldx, xoff,
-                           base, Tlen, upper, ldu, out, ldo, D, FS0, Q);
+        dim3 grid(cdiv(p.D, 256 * 4), nrows);
+        hipLaunchKernelGGL((mlp_l1_kernel<T, TU, 4>), grid, dim3(256), 0, s, tab, p.x, p.ldx,
+                           p.xoff, p.base, p.Tlen, upper, p.ldu, out, p.ldo, p.D, p.FS0, p.Q);
     }
     SRNN_LAUNCH_CHECK();
-    // (the other paths: the mask bits from the written rows)
-    if (bits)
-        return srnn_relu_bits_impl(sizeof(T) == 2 ? SRNN_BF16 : SRNN_F32, out, ldo, (int)nrows, D,
-                                   bits, ldb, s);
     return 0;
+}
+
+int l1_run(const L1Problem& p, hipStream_t s) {
+    const L1Plan pl = l1_plan(p, l1_lds_switch());
+    const bool tf = p.dtype == SRNN_F32, uf = p.upper_dtype == SRNN_F32;
+    const int rc = pl.route == SRNN_L1_LDS ? l1_run_lds(p, pl, s)
+                   : tf ? (uf ? l1_run_gather<float, float>(p, pl, s)
+                              : l1_run_gather<float, bf16>(p, pl, s))
+                        : (uf ? l1_run_gather<bf16, float>(p, pl, s)
+                              : l1_run_gather<bf16, bf16>(p, pl, s));
+    if (rc || !pl.bits_pass) return rc;
+    // the mask bits from the written rows
+    return srnn_relu_bits_impl(p.dtype, p.out, p.ldo, p.B * p.Tlen, p.D, p.bits, p.ldb, s);
+}
+
+static L1Problem l1_record(int dtype, const void* tab, const int64_t* x, int64_t ldx, int xoff,
+                           const int* base, int B, int Tlen, int upper_dtype, const void* upper,
+                           int64_t ldu, void* out, int64_t ldo, int D, int FS0, int Q) {
+    L1Problem p;
+    p.dtype = dtype; p.upper_dtype = upper_dtype;
+    p.B = B; p.Tlen = Tlen; p.D = D; p.FS0 = FS0; p.Q = Q;
+    p.tab = tab; p.x = x; p.ldx = ldx; p.xoff = xoff; p.base = base;
+    p.upper = upper; p.ldu = ldu; p.out = out; p.ldo = ldo;
+    return p;
 }
 
 int srnn_mlp_l1_impl(int dtype, const void* tab, const int64_t* x, int64_t ldx, int xoff,
@@ -354,18 +357,9 @@ int srnn_mlp_l1_impl(int dtype, const void* tab, const int64_t* x, int64_t ldx, 
     SRNN_REQUIRE(FS0 <= 32, "mlp_l1: frame_sizes[0] must be <= 32");
     SRNN_REQUIRE(upper_dtype == SRNN_F32 || upper_dtype == SRNN_BF16, "mlp_l1: bad upper dtype");
     if ((int64_t)B * Tlen <= 0) return 0;
-    if (dtype == SRNN_F32) {
-        if (upper_dtype == SRNN_F32)
-            return mlp_l1_launch<float, float>((const float*)tab, x, ldx, xoff, base, B, Tlen,
-                                               (const float*)upper, ldu, (float*)out, ldo, D, FS0, Q, s);
-        return mlp_l1_launch<float, bf16>((const float*)tab, x, ldx, xoff, base, B, Tlen,
-                                          (const bf16*)upper, ldu, (float*)out, ldo, D, FS0, Q, s);
-    }
-    if (upper_dtype == SRNN_F32)
-        return mlp_l1_launch<bf16, float>((const bf16*)tab, x, ldx, xoff, base, B, Tlen,
-                                          (const float*)upper, ldu, (bf16*)out, ldo, D, FS0, Q, s);
-    return mlp_l1_launch<bf16, bf16>((const bf16*)tab, x, ldx, xoff, base, B, Tlen,
-                                     (const bf16*)upper, ldu, (bf16*)out, ldo, D, FS0, Q, s);
+    return l1_run(l1_record(dtype == SRNN_F32 ? SRNN_F32 : SRNN_BF16, tab, x, ldx, xoff, base, B,
+                            Tlen, upper_dtype, upper, ldu, out, ldo, D, FS0, Q),
+                  s);
 }
 
 // the same with the ReLU mask of a1 as bits (u16 per 16 columns, row stride ldb) for the
@@ -377,9 +371,10 @@ extern "C" int srnn_mlp_l1_bits(const void* tab, const int64_t* x, int64_t ldx, 
     SRNN_REQUIRE(D % 16 == 0 && FS0 <= 32 && bits && (ldb >= D / 16 || (ldb == 0 && D % 64 == 0)),
                  "mlp_l1_bits: bad args (bit row stride >= D / 16, or 0 for the grouped layout)");
     if ((int64_t)B * Tlen <= 0) return 0;
-    return mlp_l1_launch<bf16, bf16>((const bf16*)tab, x, ldx, xoff, nullptr, B, Tlen,
-                                     (const bf16*)upper, ldu, (bf16*)out, ldo, D, FS0, Q,
-                                     (hipStream_t)stream, bits, ldb);
+    L1Problem p = l1_record(SRNN_BF16, tab, x, ldx, xoff, nullptr, B, Tlen, SRNN_BF16, upper, ldu,
+                            out, ldo, D, FS0, Q);
+    p.bits = bits; p.ldb = ldb;
+    return l1_run(p, (hipStream_t)stream);
 }
 
 extern "C" int srnn_mlp_l1(int dtype, const void* tab, const int64_t* x, int64_t ldx, int xoff,

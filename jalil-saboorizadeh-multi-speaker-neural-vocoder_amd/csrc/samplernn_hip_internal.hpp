@@ -32,6 +32,11 @@ static inline int env_flag(const char* name, int dflt) {
     const char* e = getenv(name);
     return (e && *e) ? atoi(e) : dflt;
 }
+// whether an environment switch is turned off: set, and its first character is '0'
+static inline bool env_off(const char* name) {
+    const char* e = getenv(name);
+    return e && e[0] == '0';
+}
 
 // persist.hip: the per-device sticky failure flag of the persistent sweeps (device pointer,
 // allocated zeroed on first use; null on a HIP error) and their spin limit (short when the

@@ -761,17 +761,15 @@ def mlp_backward(ctx, dlogp, nll=None):
     ctx.W_t = None
     csum_epi = T == torch.bfloat16 and M % 256 == 0 and \
         os.environ.get('SRNN_CSUM_EPI', '1') != '0'
-    # bf16, Q = 256: da2, dW_out and the hidden bias sums from ONE pass over dz and a2
-    # (srnn_mlp_out_bwd; the separate GEMMs fetch each of dz and a2 again).  The kernel keeps
-    # the separate calls' summation orders, so every gradient keeps its bits; db_out stays
-    # the column pass over dz (the kernel's own db_out sums in another order).
-    # SRNN_OUT_BWD_FUSED=0: the separate calls, which shapes the kernel does not serve (None)
-    # take too.  With a2's mask kept as bits (SRNN_MASK_BITS=1) the kernel still masks by
-    # the a2 it stages for dW_out -- bit m2 is a2 > 0 by construction -- so both settings
-    # return the same bits (test_mask_bits_step_bf16 compares every gradient exactly).
+    # bf16: da2, dW_out and the hidden bias sums from ONE pass over dz and a2 (srnn_mlp_out_bwd;
+    # the separate GEMMs fetch each of dz and a2 again).  The kernel keeps the separate calls'
+    # summation orders, so every gradient keeps its bits; db_out stays the column pass over dz
+    # (the kernel's own db_out sums in another order).  Shapes it does not serve (None) and
+    # SRNN_OUT_BWD_FUSED=0 take the separate calls.  With a2's mask kept as bits
+    # (SRNN_MASK_BITS=1) the kernel still masks by the a2 it stages for dW_out -- bit m2 is
+    # a2 > 0 by construction: same bits (test_mask_bits_step_bf16 compares every gradient).
     fused = None
-    if T == torch.bfloat16 and Q == 256 and D % 128 == 0 and M % 256 == 0 and \
-            W_t is not None and os.environ.get('SRNN_OUT_BWD_FUSED', '1') != '0':
+    if T == torch.bfloat16 and W_t is not None and os.environ.get('SRNN_OUT_BWD_FUSED', '1') != '0':
         ev = H.roof_begin()
         fused = H.mlp_out_bwd(dz, a2, W_t[1], want_db=False)
         if fused is not None:
@@ -819,7 +817,8 @@ def mlp_backward(ctx, dlogp, nll=None):
             amax = None
     # folded embedding . conv backward: dTab[q][k][:] += da1[t] for x_{t+k} = q
     dtabT = torch.empty((Q, FS0 * D), device=dev, dtype=T)
-    work = torch.empty(Q * FS0 * D, device=dev, dtype=torch.int64)
+    work = torch.empty(H.mlp_dtab_plan(da1.dtype, T, B, Tl, D, FS0, Q).work_bytes // 8,
+                       device=dev, dtype=torch.int64)
     # the same pass sums da1 over rows t = j (mod FS0): the bottom tier's upsampling bias
     # gradient (its output is this layer's `upper`), handed over on the returned gradient
     colsum = torch.empty(FS0 * D, device=dev, dtype=torch.float32)

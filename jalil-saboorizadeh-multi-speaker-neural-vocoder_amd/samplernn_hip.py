@@ -5,6 +5,7 @@ there is no PyTorch or CPU fallback for device tensors.  If the library is missi
 fails to load, `lib()` raises -- loudly -- and so does every op that needs it.
 PyTorch is used for device memory, streams and autograd bookkeeping only.
 """
+import collections
 import ctypes
 import sys
 import time
@@ -54,6 +55,12 @@ _SIGS = {
                        ctypes.POINTER(_I), _P, _P],
     'srnn_mlp_dtab4': [_I, _P, _L, _P, _L, _I, _I, _I, _P, _I, _I, _I, _I, _P, _SZ, _P,
                        ctypes.POINTER(_I), _P, _P, _P],
+    'srnn_mlp_dtab_plan': [_I, _I, _I, _I, _I, _I, _I, _L, _I, _I, _SZ] +
+                          [ctypes.POINTER(_I)] * 6 + [ctypes.POINTER(_SZ)],
+    'srnn_mlp_dtab_plan_for': [_I, _I, _I, _I, _I, _I, _I, _L, _I, _I, _SZ, _I] +
+                              [ctypes.POINTER(_I)] * 6 + [ctypes.POINTER(_SZ)],
+    'srnn_mlp_l1_plan_for': [_I, _I, _I, _I, _I, _I, _I, _P, _P, _L, _P, _L, _I, _I,
+                             ctypes.POINTER(_I), ctypes.POINTER(_I)],
     'srnn_cast_multi': [_I, _P, _P, _P, _P],
     'srnn_logsoftmax_nll': [_P, _L, _P, _L, _I, _L, _I, _P, _P, _L, _P, _I, _L, _F, _P],
     'srnn_logsoftmax_bwd': [_P, _L, _P, _L, _L, _I, _P, _I, _L, _P],
@@ -432,6 +439,45 @@ def gru_layer_plan(dtype, B, D):
     lib().call('srnn_gru_layer_plan', dcode(dtype), B, D, ctypes.byref(be), ctypes.byref(fb),
                ctypes.byref(bb))
     return GRU_BACKENDS[be.value], fb.value, bb.value
+
+
+DTAB_ROUTES = ('empty', 'generic', 'posws', 'direct', 'packed')   # the C ABI's SrnnDtabRoute
+L1_ROUTES = ('generic', 'xcd', 'lds')                               # the C ABI's SrnnL1Route
+DtabPlan = collections.namedtuple('DtabPlan', 'route cw pd x8 use_blk colsum work_bytes')
+L1Plan = collections.namedtuple('L1Plan', 'route bits_pass')
+
+
+def mlp_dtab_plan(dtype, out_dtype, B, Tl, D, FS0, Q, ldda=None, have_amax=False,
+                  have_blk=False, work_bytes=None, packed_ok=None):
+    """The plan of srnn_mlp_dtab4 for this call (csrc/mlp_plan.hpp): the route among
+    DTAB_ROUTES, the generic column width, the packed form's prefetch depth, whether it stages
+    byte windows (x8) and reads blk, whether the route writes the column sums, and the bytes
+    of work the call requires.  ldda defaults to D, work_bytes to what the plan asks for.
+    packed_ok: srnn_dtab_packed_ok()'s answer, None to ask this device.  The SRNN_DTAB_*
+    switches are read per call."""
+    out = [_I(0) for _ in range(6)] + [_SZ(0)]
+    args = [dcode(dtype), dcode(out_dtype), B, Tl, D, FS0, Q, D if ldda is None else ldda,
+            int(have_amax), int(have_blk), _SZ(-1).value if work_bytes is None else work_bytes]
+    refs = [ctypes.byref(o) for o in out]
+    if packed_ok is None:
+        lib().call('srnn_mlp_dtab_plan', *args, *refs)
+    else:
+        lib().call('srnn_mlp_dtab_plan_for', *args, int(packed_ok), *refs)
+    r, cw, pd, x8, blk, cs, need = (o.value for o in out)
+    return DtabPlan(DTAB_ROUTES[r], cw, pd, bool(x8), bool(blk), bool(cs), need)
+
+
+def mlp_l1_plan(dtype, upper_dtype, B, Tl, D, FS0, Q, tab, upper, ldu, out, ldo,
+                have_base=False, have_bits=False):
+    """The plan of srnn_mlp_l1 / srnn_mlp_l1_bits for this call: the route among L1_ROUTES and
+    whether the mask bits take a separate pass.  tab / upper / out: tensors or plain addresses,
+    looked at for their alignment only.  SRNN_L1_LDS is read per call."""
+    addr = lambda a: a if isinstance(a, int) else ptr(a)                # noqa: E731
+    route, bp = _I(0), _I(0)
+    lib().call('srnn_mlp_l1_plan_for', dcode(dtype), dcode(upper_dtype), B, Tl, D, FS0, Q,
+               addr(tab), addr(upper), ldu, addr(out), ldo, int(have_base), int(have_bits),
+               ctypes.byref(route), ctypes.byref(bp))
+    return L1Plan(L1_ROUTES[route.value], bool(bp.value))
 
 
 def _gru_query(name, restype, dtype, B, D):

@@ -203,8 +203,8 @@ def l1case(dtype, udtype, B, Tl, D, FS0=16, Q=256, places=None, env=None, **kw):
 
 
 def l1_route(c):
-    """The kernel mlp_l1_launch takes for this case, recomputed from its conditions
-    (csrc/mlp.hip): 'lds', 'xcd' or 'generic'."""
+    """The kernel that serves this case, 'lds', 'xcd' or 'generic': stated here independently
+    of the library, whose l1_plan (csrc/mlp_plan.cpp) test_cpu_mlp_plan.py holds to it."""
     es, ue = (4 if c.dtype == 'f32' else 2), (4 if c.udtype == 'f32' else 2)
     nrows = c.B * c.Tl
     pu, po = PLACEMENTS[c.placement('upper')], PLACEMENTS[c.placement('out')]
@@ -333,8 +333,9 @@ def pk_lds_bytes(Q, Tl):
 
 
 def dtab_route(c):
-    """The path srnn_mlp_dtab4 takes, recomputed from its conditions (csrc/dtab.hip):
-    'packed', 'direct', 'posws' (position-major with workspace), 'generic<cw>' or 'empty'."""
+    """The path srnn_mlp_dtab4 takes, 'packed', 'direct', 'posws' (position-major with
+    workspace), 'generic<cw>' or 'empty': stated here independently of the library, whose
+    dtab_plan (csrc/mlp_plan.cpp) test_cpu_mlp_plan.py holds to it."""
     env = dict(c.env)
     off = lambda k: env.get(k, '1')[:1] == '0'                          # noqa: E731
     n = c.B * c.Tl

@@ -9,9 +9,10 @@ reference and a bf16 output to its round-to-nearest-even; every operand and outp
 window in a canary-filled buffer, index streams included, so stray reads poison the result
 and stray writes show.
 
-The tests cannot see which kernel served a case and do not need to: the tables put a shape
-on each side of every condition of the dispatchers (mlp_l1_launch, srnn_mlp_dtab4,
-srnn_mlp_out_bwd, srnn_nll_bwd), so whichever kernel serves a shape has to be right.
+The tables put a shape on each side of every condition of the dispatchers (l1_plan, dtab_plan,
+srnn_mlp_out_bwd, srnn_nll_bwd), so whichever kernel serves a shape has to be right; the L1
+and dTab cases also ask the library's plan with their real operands first and fail if the
+route is not the one their table is named for.
 tests/test_cpu_mlp_cases.py proves on the CPU that every case is exact by itself and that
 the tables do lie on both sides of those conditions.
 
@@ -184,6 +185,12 @@ def _p(x):
 def run_l1(hip, t):
     c, w = t.case, t.w
     x = w['x']
+    # the library's own plan for these operands: the kernel the table names the case for
+    plan = hip.mlp_l1_plan(w['out'].dtype, w['upper'].dtype, c.B, c.Tl, c.D, c.FS0, c.Q,
+                           _p(w['tab']), _p(w['upper']), w['upper'].ld, _p(w['out']), w['out'].ld,
+                           have_bits=bool(c.bits))
+    if plan.route != C.l1_route(c):
+        return '%s: planned %s, the table says %s' % (c.id, plan.route, C.l1_route(c))
     if c.bits:
         hip.lib().call('srnn_mlp_l1_bits', _p(w['tab']), _p(x), x.ld, x.xoff, c.B, c.Tl,
                        _p(w['upper']), w['upper'].ld, _p(w['out']), w['out'].ld, c.D, c.FS0, c.Q,
@@ -201,6 +208,13 @@ def run_dtab(hip, t):
     x = w['x']
     work = torch.empty(t.work_elems, device=DEV, dtype=torch.int64)     # scratch, not an operand
     done = ctypes.c_int(-1)
+    # the library's own plan on this device: the route the table names the case for
+    plan = hip.mlp_dtab_plan(w['da'].dtype, w['dtab'].dtype, c.B, c.Tl, c.D, c.FS0, c.Q,
+                             ldda=w['da'].ld, have_amax='amax' in w, have_blk='blk' in w,
+                             work_bytes=work.numel() * 8)
+    route = plan.route + (str(plan.cw) if plan.route == 'generic' else '')
+    if route != t.route:
+        return '%s: planned %s, the table says %s' % (c.id, route, t.route)
     head = (hip.dcode(w['da'].dtype), _p(w['da']), w['da'].ld, _p(x), x.ld, x.xoff, c.B, c.Tl,
             _p(w['dtab']), hip.dcode(w['dtab'].dtype), c.D, c.FS0, c.Q, hip.ptr(work),
             work.numel() * 8)
