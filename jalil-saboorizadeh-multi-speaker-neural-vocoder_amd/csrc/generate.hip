@@ -471,10 +471,13 @@ struct GenSwitches {
 };
 
 // fp32 too (SRNN_GEN_FOLD_F32=0: unfolded fp32 ticks): the folds reassociate fp32 sums
-// (W_ih (W_in a + b) -> (W_ih W_in) a + W_ih b), same precision, rounding in the last bits
+// (W_ih (W_in a + b) -> (W_ih W_in) a + W_ih b), same precision, rounding in the last bits.
+// The folded upper tick hands its carried gh to the GRU cell, which takes a precomputed gh in
+// its ring form only: dim a multiple of the ring's k stage, 256 bytes (128 in bf16, 64 in fp32);
+// other widths keep the unfolded ticks.
 bool fold_ok(const SrnnModel* m, const GenSwitches& sw) {
     const SrnnTier& t = m->tier[0];
-    return (m->dtype == SRNN_BF16 || (sw.fold_f32 && m->dim % 64 == 0)) &&
+    return (m->dtype == SRNN_BF16 ? m->dim % 128 == 0 : (sw.fold_f32 && m->dim % 64 == 0)) &&
            m->n_tiers >= 2 &&
            m->n_rnn == 1 &&
            t.in_dim == t.n_frame_samples && t.n_frame_samples <= 16 && t.b_up &&

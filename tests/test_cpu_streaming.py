@@ -185,14 +185,15 @@ def test_library_exports_the_streaming_entry_points():
         assert hasattr(dll, name), name
         assert name in H._SIGS and name in H.exported_symbols()
     assert dll.srnn_abi_version() == 2
-    # the state size: a multiple of the row count, 0 on bad arguments; a folded bf16 model
-    # carries the two 3 D gh rows an unfolded fp32 one (dim not a multiple of 64) does not
+    # the state size: a multiple of the row count, 0 on bad arguments; a folded model carries
+    # the two 3 D gh rows an unfolded one does not, and the ticks fold where the GRU cell takes
+    # the carried gh: dim a multiple of 128 in bf16, of 64 in fp32
     import custom_ops
-    meta = [2, 1, 48, 256, 43, H.BF16, 16, 16, 16, 1, 4, 64, 107, 0, 64]
-    folded = custom_ops.gen_state_row_bytes(meta)
-    meta[5] = H.F32
-    plain = custom_ops.gen_state_row_bytes(meta)
-    assert plain == 4 * (16 + 64 + 2 * 48) and folded == plain + 4 * 6 * 48
+    for D, dt, fold in ((128, H.BF16, True), (128, H.F32, True), (64, H.F32, True),
+                        (64, H.BF16, False), (48, H.BF16, False), (48, H.F32, False)):
+        meta = [2, 1, D, 256, 43, dt, 16, 16, 16, 1, 4, 64, 107, 0, 64]
+        plain = 4 * (16 + 64 + 2 * D)
+        assert custom_ops.gen_state_row_bytes(meta) == plain + (4 * 6 * D if fold else 0), (D, dt)
     dll.srnn_gen_state_bytes.restype = ctypes.c_size_t
     dll.srnn_gen_state_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int]
     m = H.SrnnModel()

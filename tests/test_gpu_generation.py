@@ -8,6 +8,10 @@ model.py:445-520).
   exactly argmax(exp(logp) / q) of the log-probs the loop reports, and those log-probs are
   the teacher-forced fp32 Predictor's on the generated stream within a bf16 tolerance;
 * shapes with a ragged last row group (B not a multiple of R).
+
+These tests bound the bf16 loop loosely and compare paths with one another; for exactness -- the
+whole index stream, the carried state and every step's log-probs against a float64 reference,
+over every kernel form, association and path -- see tests/test_gpu_gen_conformance.py.
 """
 import numpy as np
 import pytest

@@ -27,7 +27,7 @@ F32, BF16 = torch.float32, torch.bfloat16
 
 # recipe.CONFIGS entries, dim raised to where the ticks fold: a multiple of 64 in fp32, and of
 # 128 in bf16 (the GRU cell kernel that takes the folded ticks' precomputed gh needs whole
-# 256-byte k stages; a bf16 model at dim 64 does not generate at all)
+# 256-byte k stages; a bf16 model at dim 64 keeps the unfolded ticks)
 CFGS = {
     't3': dict(recipe.CONFIGS['t3'], dim=64),          # fold + fold_top
     't3x128': dict(recipe.CONFIGS['t3'], dim=128),
