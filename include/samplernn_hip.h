@@ -611,6 +611,14 @@ int srnn_gen_persistent_rows_level(int dtype, int n_seqs, int dim, int fs0, int 
 int srnn_sample_rows(const float* logits, int64_t ld, int rows, const float* noise, uint64_t seed,
                      int row0, int step, const float* temperature, const int32_t* top_k,
                      const float* top_p, int64_t* index, float* logp, void* stream);
+/* srnn_sample_rows that also writes the rows' score pairs: score (rows, 2) fp32, 8-byte aligned,
+ * {log-prob of the row's drawn index, entropy of softmax(logits) in nats}, both of the model's
+ * own distribution whatever the controls (score[0] is logp[index], bit for bit).  Given, it
+ * selects the scored instantiation (level 3); NULL: exactly srnn_sample_rows, same kernels.    */
+int srnn_sample_rows2(const float* logits, int64_t ld, int rows, const float* noise,
+                      uint64_t seed, int row0, int step, const float* temperature,
+                      const int32_t* top_k, const float* top_p, int64_t* index, float* logp,
+                      void* stream, float* score);
 
 /* ---- streaming: carried state and a forced prefix ------------------------------------------
  * Bytes of the opaque recurrent state of n_seqs rows of model m as srnn_generate5 reads and
@@ -692,6 +700,23 @@ int srnn_generate6(const SrnnModel* m, int n_seqs, int n_cond, const float* cond
                    void* stream, const float* temperature, const int32_t* top_k,
                    const float* top_p, const SrnnGenStream* st, const SrnnGenRows* rows);
 
+/* srnn_generate6 that also writes every step's score pair: score (n_cond * L, n_seqs, 2) fp32,
+ * device, 8-byte aligned, indexed as logp is (step * n_seqs + b):
+ *   score[0]  log-prob of the step's sample -- the index drawn, or the caller's sample at a
+ *             forced step -- equal to logp[step, b, sample] bit for bit
+ *   score[1]  entropy of the model's softmax at that step, in nats, never negative
+ * Both describe the model's own distribution, whatever temperature, top_k and top_p did to the
+ * draw.  8 bytes per row-step where logp takes 1,024: with every step forced (st->n_forced) the
+ * call scores given audio.  score given selects the samplers' scored instantiations (level 3:
+ * level 2 plus the pair; default controls draw the plain stream bit for bit); with score NULL it
+ * is exactly srnn_generate6 (same kernels).  srnn_gen_persistent_rows_level answers for level 3. */
+int srnn_generate7(const SrnnModel* m, int n_seqs, int n_cond, const float* cond,
+                   const float* row_bias, const float* noise, uint64_t seed, int row0,
+                   int64_t* seq, float* logp, void* workspace, size_t workspace_bytes, int flags,
+                   void* stream, const float* temperature, const int32_t* top_k,
+                   const float* top_p, const SrnnGenStream* st, const SrnnGenRows* rows,
+                   float* score);
+
 /* Writes to state_out (device, state_bytes = srnn_gen_state_bytes(m, n_seqs), 8-byte aligned)
  * the records of n_seqs rows that have done no step: this process's header, step count 0, a
  * q_zero history (q_levels / 2), h0 of every tier and layer and, with folded ticks, their carried
@@ -721,6 +746,9 @@ typedef struct SrnnGenSession SrnnGenSession;
 #define SRNN_GEN_SESSION_PER_SAMPLE 2   /* per-sample kernels, not the persistent sample loop */
 #define SRNN_GEN_SESSION_LOGP       4   /* chunks may ask for log-probs                       */
 #define SRNN_GEN_SESSION_NOISE      8   /* every chunk brings replayed noise (no Philox)      */
+#define SRNN_GEN_SESSION_SCORE     16   /* chunks may ask for score pairs (srnn_generate7): the
+                                         * session's level must then be 3, and only then; the
+                                         * arena grows by max_frames * L * n_seqs * 8 bytes    */
 
 /* Arena bytes of a session.  Domains: n_seqs >= 1, max_frames >= 1, level in {0, 1, 2} (the
  * sampling controls its chunks may carry: 0 none, 1 temperature / top_k / a forced prefix, 2
@@ -771,6 +799,13 @@ typedef struct SrnnGenChunk {
  * given; 2 on a HIP error, which poisons the session: this and every later call return 2 with
  * the first error's text and launch nothing.                                                  */
 int srnn_gen_session_chunk(SrnnGenSession* s, const SrnnGenChunk* chunk, void* stream);
+/* srnn_gen_session_chunk that also writes the chunk's score pairs (n_frames * L, n_seqs, 2),
+ * srnn_generate7's, to score_out (device or pinned host memory), as logp_out is written.  A
+ * score asked of a session opened without SRNN_GEN_SESSION_SCORE returns 1 with a message,
+ * nothing queued.  A session opened with the flag has level 3 (every control and a forced prefix
+ * allowed).  score_out NULL: srnn_gen_session_chunk.                                          */
+int srnn_gen_session_chunk2(SrnnGenSession* s, const SrnnGenChunk* chunk, float* score_out,
+                            void* stream);
 /* Waits for the session's queued work; 2 (and a poisoned session) where it failed or the
  * persistent sample loop raised its error word, as srnn_generate reports it.                   */
 int srnn_gen_session_sync(SrnnGenSession* s);

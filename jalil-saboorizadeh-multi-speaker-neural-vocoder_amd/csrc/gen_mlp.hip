@@ -248,8 +248,9 @@ __device__ __forceinline__ void gmt_grid_barrier(int* bar, int nblk, int epoch, 
 // TG: the bottom tick's GEMM runs in this launch before the sample loop (GenMlpArgs::tg;
 // bf16 only), with the prologue's resident-fragment loads in flight beside it.
 // CT: the level of the rows' sampling controls in the draw -- 1: GenMlpArgs::temperature /
-// top_k, 2: those and top_p -- builds of their own, launched only when a control array of that
-// level is given: without one the kernels that run are the plain ones (0), unchanged.
+// top_k, 2: those and top_p, 3: level 2 plus the step's score pair (GenMlpArgs::score) --
+// builds of their own, launched only when a control array of that level (or the score buffer)
+// is given: without one the kernels that run are the plain ones (0), unchanged.
 template <typename T, int UPW, int NT, int NZT, int MAXT, int FS0C, int DC, bool TG = false,
           int CT = 0>
 __global__ __launch_bounds__(gm::NTHR, 2) void gen_mlp_kernel(GenMlpArgs a) {
@@ -278,7 +279,7 @@ __global__ __launch_bounds__(gm::NTHR, 2) void gen_mlp_kernel(GenMlpArgs a) {
     const T* wol = (const T*)((char*)gsh + 16);
     // CT: the group's rows' sampling controls {tau, k} x 8 rows sit at the very end of the
     // dynamic LDS (read once in the prologue: the loop holds neither array's pointer nor the
-    // values in registers -- it has none to spare -- and no other offset moves); CT = 2: the
+    // values in registers -- it has none to spare -- and no other offset moves); CT >= 2: the
     // rows' p x 8 follow them (96 B in all)
     int* ctl = (int*)((char*)gsh + 16 + (WOL ? (size_t)NZ * (D + 8) * sizeof(T) : 0) +
                       (TG ? (size_t)gmt::LDS : 0));
@@ -638,7 +639,7 @@ __global__ __launch_bounds__(gm::NTHR, 2) void gen_mlp_kernel(GenMlpArgs a) {
             const int kb = a.top_k ? a.top_k[b] : 0;
             const int nf = a.n_forced ? min(max(a.n_forced[b], 0), (1 << 23) - 1) : 0;
             ctl[2 * tid + 1] = (int)((uint32_t)(kb >= 1 && kb <= 255 ? kb : 0) | ((uint32_t)nf << 8));
-            if constexpr (CT == 2)
+            if constexpr (CT >= 2)
                 ctl[16 + tid] = (int)__float_as_uint(a.top_p ? a.top_p[b] : 1.0f);
         }
     }
@@ -928,15 +929,28 @@ __global__ __launch_bounds__(gm::NTHR, 2) void gen_mlp_kernel(GenMlpArgs a) {
                 const int rc = __builtin_amdgcn_readfirstlane(min(r, 7));
                 const int2 ck = *reinterpret_cast<const int2*>(ctl + 2 * rc);
                 const int kk = ck.y & 255;
-                if constexpr (CT == 2)
+                if constexpr (CT == 3) {
+                    // scored build: the level-2 draw, then the pair of the step's sample (the
+                    // forced one at a forced step) and the dense row, if asked, from one pass
+                    floatx4 zz;
+                    x = sample_row_ctrl_z(v, lq, __uint_as_float((uint32_t)ck.x), kk,
+                                          __uint_as_float((uint32_t)ctl[16 + rc]), zz, lane);
+                    forced = i - a.L < (int)((uint32_t)ck.y >> 8);
+                    if (forced) x = (int)a.seq[(int64_t)min(b, B - 1) * a.ldseq + i] & (Q - 1);
+                    const float2 sc = row_score(zz, x, lrow, lane);
+                    if (p == 0 && valid && a.score && lane == 0)
+                        *reinterpret_cast<float2*>(a.score + ((int64_t)(i - a.L) * B + b) * 2) = sc;
+                } else if constexpr (CT == 2)
                     x = sample_row_ctrl(v, lq, __uint_as_float((uint32_t)ck.x), kk,
                                         __uint_as_float((uint32_t)ctl[16 + rc]), lrow, lane);
                 else
                     x = sample_row_ctrl(v, lq, __uint_as_float((uint32_t)ck.x), kk, lrow, lane);
                 // forced prefix: the step keeps the caller's sample (the log-probs above are
                 // written, the noise was consumed); wave-uniform, before hist is written
-                forced = i - a.L < (int)((uint32_t)ck.y >> 8);
-                if (forced) x = (int)a.seq[(int64_t)min(b, B - 1) * a.ldseq + i] & (Q - 1);
+                if constexpr (CT != 3) {
+                    forced = i - a.L < (int)((uint32_t)ck.y >> 8);
+                    if (forced) x = (int)a.seq[(int64_t)min(b, B - 1) * a.ldseq + i] & (Q - 1);
+                }
             } else {
                 x = sample_row(v, lq, lrow, lane);
             }
@@ -1089,12 +1103,14 @@ int gen_mlp_plan(int dtype, int B, int D, int FS0, int Q, int ctrl, GenMlpPlan* 
     if (!R) return 0;
     // (the kernels recorded here are the ones gen_mlp_launch starts and asks the occupancy
     //  of: with controls, their own instantiations)
-    if (ctrl < 0 || ctrl > 2) return 0;
+    if (ctrl < 0 || ctrl > 3) return 0;
     const GmKernel k = dtype == SRNN_BF16
-                           ? (ctrl == 2   ? pick<bf16, 2>(upw, NZ / 16, FS0, D, R)
+                           ? (ctrl == 3   ? pick<bf16, 3>(upw, NZ / 16, FS0, D, R)
+                              : ctrl == 2 ? pick<bf16, 2>(upw, NZ / 16, FS0, D, R)
                               : ctrl == 1 ? pick<bf16, 1>(upw, NZ / 16, FS0, D, R)
                                           : pick<bf16, 0>(upw, NZ / 16, FS0, D, R))
-                           : (ctrl == 2   ? pick<float, 2>(upw, NZ / 16, FS0, D, R)
+                           : (ctrl == 3   ? pick<float, 3>(upw, NZ / 16, FS0, D, R)
+                              : ctrl == 2 ? pick<float, 2>(upw, NZ / 16, FS0, D, R)
                               : ctrl == 1 ? pick<float, 1>(upw, NZ / 16, FS0, D, R)
                                           : pick<float, 0>(upw, NZ / 16, FS0, D, R));
     if (!k) return 0;
@@ -1105,7 +1121,8 @@ int gen_mlp_plan(int dtype, int B, int D, int FS0, int Q, int ctrl, GenMlpPlan* 
     if (dtype == SRNN_BF16 && FS0 == 16 && D == 1024 && R == 8 && Q == gm::Q &&
         env_flag("SRNN_GEN_TICK_GEMM", 1))
         pl->kernel_tg =
-            ctrl == 2   ? (const void*)gen_mlp_kernel<bf16, 4, 4, 2, 15, 16, 1024, true, 2>
+            ctrl == 3   ? (const void*)gen_mlp_kernel<bf16, 4, 4, 2, 15, 16, 1024, true, 3>
+            : ctrl == 2 ? (const void*)gen_mlp_kernel<bf16, 4, 4, 2, 15, 16, 1024, true, 2>
             : ctrl == 1 ? (const void*)gen_mlp_kernel<bf16, 4, 4, 2, 15, 16, 1024, true, 1>
                         : (const void*)gen_mlp_kernel<bf16, 4, 4, 2, 15, 16, 1024, true>;
     const int es = dtype == SRNN_BF16 ? 2 : 4;
@@ -1115,7 +1132,7 @@ int gen_mlp_plan(int dtype, int B, int D, int FS0, int Q, int ctrl, GenMlpPlan* 
     lds += (size_t)KW * ntm * 32 * 16;                // rows 0..7 of the 16-row tiles (R = 8)
     lds += (size_t)R * gm::HIST * 4;
     lds += 16;                                        // group / member / mode words
-    if (ctrl) lds += ctrl == 2 ? 96 : 64;             // the rows' controls (gen_mlp_kernel CT)
+    if (ctrl) lds += ctrl >= 2 ? 96 : 64;             // the rows' controls (gen_mlp_kernel CT)
     if (dtype == SRNN_F32 && upw > 4)                 // W_out slice in LDS (gen_mlp_kernel WOL)
         lds += (size_t)NZ * (D + 8) * 4;
     if (lds > 160 * 1024) return 0;
@@ -1236,7 +1253,8 @@ int gen_mlp_launch(const GenMlpPlan* pl, GenMlpArgs a, bool row_origins, hipStre
     // SRNN_GEN_LOCAL=0 only forces the global-mode hand-offs
     SRNN_REQUIRE(a.census && pl->G * pl->P <= HX_KEYED_WORDS, "gen_mlp: no census array");
     a.nolocal = pl->local ? 0 : 1;
-    SRNN_REQUIRE(pl->ctrl == sample_ctrl_level(a.temperature, a.top_k, a.top_p, a.n_forced),
+    SRNN_REQUIRE(pl->ctrl == sample_ctrl_level(a.temperature, a.top_k, a.top_p, a.n_forced,
+                                               a.score),
                  "gen_mlp: plan and sampling-control arrays disagree");
     {
         // SRNN_GEN_DIAG=1: phase timestamps of the first launch into a device buffer that

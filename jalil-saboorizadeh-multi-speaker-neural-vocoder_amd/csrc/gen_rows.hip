@@ -43,13 +43,50 @@ __global__ __launch_bounds__(256) void sample_origin_kernel(
     if (lane == 0) seq[(int64_t)b * ldseq + i] = bi;
 }
 
+// The scored build (level 3), mlp.hip's sample_scored_kernel plus the two arrays
+__global__ __launch_bounds__(256) void sample_origin_scored_kernel(
+    const float* __restrict__ z, int64_t ldz, int B, const float* __restrict__ noise,
+    uint64_t seed, int row0, const int* __restrict__ base, int off, int L,
+    int64_t* __restrict__ seq, int64_t ldseq, float* __restrict__ logp_out,
+    const float* __restrict__ temperature, const int* __restrict__ top_k,
+    const float* __restrict__ top_p, uint32_t step0, const int* __restrict__ n_forced,
+    const int* __restrict__ noise_row, const uint32_t* __restrict__ row_step0,
+    float* __restrict__ score) {
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (b >= B) return;
+    const int i = *base + off;
+    const int step = i - L;
+    const floatx4 v = *reinterpret_cast<const floatx4*>(z + (int64_t)b * ldz + 4 * lane);
+    const floatx4 lq = log_noise(sample_noise(noise, seed, B, b, step, lane, row0, step0,
+                                              noise_row, row_step0));
+    float* lrow = logp_out ? logp_out + ((int64_t)step * B + b) * 256 : nullptr;
+    floatx4 zz;
+    int bi = sample_row_ctrl_z(v, lq, temperature ? temperature[b] : 1.0f, top_k ? top_k[b] : 0,
+                               top_p ? top_p[b] : 1.0f, zz, lane);
+    const bool forced = n_forced && step < n_forced[b];
+    if (forced) bi = (int)seq[(int64_t)b * ldseq + i] & 255;
+    const float2 sc = row_score(zz, bi, lrow, lane);
+    if (lane == 0) {
+        *reinterpret_cast<float2*>(score + ((int64_t)step * B + b) * 2) = sc;
+        if (!forced) seq[(int64_t)b * ldseq + i] = bi;
+    }
+}
+
 int srnn_sample_origin_impl(const float* z, int64_t ldz, int B, const float* noise,
                             uint64_t seed, int row0, const int* base, int off, int L,
                             int64_t* seq, int64_t ldseq, float* logp_out,
                             const float* temperature, const int* top_k, const float* top_p,
                             uint32_t step0, const int* n_forced, const int* noise_row,
-                            const uint32_t* row_step0, hipStream_t s) {
-    const int lv = sample_ctrl_level(temperature, top_k, top_p, n_forced);
+                            const uint32_t* row_step0, float* score, hipStream_t s) {
+    const int lv = sample_ctrl_level(temperature, top_k, top_p, n_forced, score);
+    if (lv == 3) {
+        hipLaunchKernelGGL(sample_origin_scored_kernel, dim3(cdiv(B, 4)), dim3(256), 0, s, z, ldz,
+                           B, noise, seed, row0, base, off, L, seq, ldseq, logp_out, temperature,
+                           top_k, top_p, step0, n_forced, noise_row, row_step0, score);
+        SRNN_LAUNCH_CHECK();
+        return 0;
+    }
     auto k = lv == 2 ? sample_origin_kernel<2>
                      : lv == 1 ? sample_origin_kernel<1> : sample_origin_kernel<0>;
     hipLaunchKernelGGL(k, dim3(cdiv(B, 4)), dim3(256), 0, s, z, ldz, B, noise, seed, row0, base,

@@ -26,13 +26,14 @@ int srnn_sample_impl(const float* z, int64_t ldz, int B, const float* noise, uin
                      int row0,
                      const int* base, int off, int L, int64_t* seq, int64_t ldseq,
                      float* logp_out, const float* temperature, const int* top_k,
-                     const float* top_p, uint32_t step0, const int* n_forced, hipStream_t s);
+                     const float* top_p, uint32_t step0, const int* n_forced, float* score,
+                     hipStream_t s);
 int srnn_sample_origin_impl(const float* z, int64_t ldz, int B, const float* noise,
                             uint64_t seed, int row0, const int* base, int off, int L,
                             int64_t* seq, int64_t ldseq, float* logp_out,
                             const float* temperature, const int* top_k, const float* top_p,
                             uint32_t step0, const int* n_forced, const int* noise_row,
-                            const uint32_t* row_step0, hipStream_t s);
+                            const uint32_t* row_step0, float* score, hipStream_t s);
 int gen_rows_step0_launch(const void* records, int64_t rw, int word, int B, uint32_t* step0,
                           hipStream_t s);
 int gen_rows_err_launch(const int* err, int* sticky, hipStream_t s);
@@ -588,8 +589,11 @@ struct GenRequest {
     const int* n_forced = nullptr;        // per-row forced prefix lengths (device), or null
     const int* noise_row = nullptr;       // per-row Philox row (device, n_seqs), or null: row0 + b
     const uint32_t* row_step0 = nullptr;  // per-row Philox step origin (device), or null: step0
+    float* score = nullptr;               // (n_cond L, n_seqs, 2) score pairs (device), or null
     bool row_origins() const { return noise_row || row_step0; }
-    int level() const { return sample_ctrl_level(temperature, top_k, top_p, n_forced); }
+    int level() const {
+        return sample_ctrl_level(temperature, top_k, top_p, n_forced, score);
+    }
 };
 
 // f(T{}) launches a kernel's instantiation for T, the element type of `dtype`
@@ -824,10 +828,10 @@ int mlp_step(Ctx& c, int off) {
         return srnn_sample_origin_impl(c.b.logits, Q, B, r.noise, r.seed, r.row0, c.b.base, off,
                                        c.L, r.seq, c.ldseq, r.logp, r.temperature, r.top_k,
                                        r.top_p, r.step0, r.n_forced, r.noise_row, r.row_step0,
-                                       c.s);
+                                       r.score, c.s);
     RET(srnn_sample_impl(c.b.logits, Q, B, r.noise, r.seed, r.row0, c.b.base, off, c.L, r.seq,
                          c.ldseq, r.logp, r.temperature, r.top_k, r.top_p, r.step0, r.n_forced,
-                         c.s));
+                         r.score, c.s));
     return 0;
 }
 
@@ -862,7 +866,7 @@ int run_block(Ctx& c, int periods) {
             a.xa1 = c.b.xa1; a.xa2 = c.b.xa2; a.xz = c.b.xz; a.err = c.b.gerr;
             a.census = c.b.gerr + 64;
             a.temperature = r.temperature; a.top_k = r.top_k; a.top_p = r.top_p;
-            a.step0 = r.step0; a.n_forced = r.n_forced;
+            a.step0 = r.step0; a.n_forced = r.n_forced; a.score = r.score;
             // (a streamed call on the plain kernels always draws ahead: their in-loop draw,
             //  kept as it was, knows no step origin; nor does any build's know per-row origins)
             if (c.b.lq && (c.sw.noise_ahead || (r.step0 != 0 && !c.pl->ctrl) ||
@@ -1343,10 +1347,11 @@ struct SessBufs {
     float* temperature;      // (B) each; level >= 1
     int* top_k;
     int* n_forced;
-    float* top_p;            // level 2
+    float* top_p;            // level >= 2
     int* noise_row;
     uint32_t* step0;
     float* logp;             // (F L, B, Q), SRNN_GEN_SESSION_LOGP
+    float* score;            // (F L, B, 2), SRNN_GEN_SESSION_SCORE
     float* noise;            // (F L, B, Q), SRNN_GEN_SESSION_NOISE
     uint32_t* records;       // (B, rw)
     int* sticky;             // the first error word a chunk's persistent loop raised
@@ -1358,8 +1363,11 @@ struct SessBufs {
 // size and, given the arena, its carving.
 int session_carve(const SrnnModel* m, int B, int F, int level, int flags, const GenSwitches& sw,
                   char* arena, SessBufs* sb, size_t* bytes) {
-    SRNN_REQUIRE(m && B > 0 && F > 0 && level >= 0 && level <= 2 && !(flags & ~15),
+    SRNN_REQUIRE(m && B > 0 && F > 0 && level >= 0 && level <= 3 && !(flags & ~31),
                  "gen_session: bad args");
+    // (level 3 is the scored level: the flag and the level go together)
+    SRNN_REQUIRE((level == 3) == !!(flags & SRNN_GEN_SESSION_SCORE),
+                 "gen_session: level 3 and SRNN_GEN_SESSION_SCORE go together");
     SRNN_REQUIRE(m->n_tiers >= 1 && m->n_tiers <= SRNN_MAX_TIERS, "generate: n_tiers");
     SRNN_REQUIRE(m->n_rnn >= 1 && m->n_rnn <= SRNN_MAX_RNN, "generate: n_rnn");
     SRNN_REQUIRE(m->q_levels == 256, "generate: q_levels must be 256");
@@ -1389,6 +1397,8 @@ int session_carve(const SrnnModel* m, int B, int F, int level, int flags, const 
     sb->step0 = (uint32_t*)take(Bz * 4);
     sb->logp = (flags & SRNN_GEN_SESSION_LOGP) ? (float*)take(steps * Bz * 256 * 4) : nullptr;
     sb->noise = (flags & SRNN_GEN_SESSION_NOISE) ? (float*)take(steps * Bz * 256 * 4) : nullptr;
+    // (after every older array: a session without the flag is carved as it always was)
+    sb->score = (flags & SRNN_GEN_SESSION_SCORE) ? (float*)take(steps * Bz * 8) : nullptr;
     sb->records = (uint32_t*)take((size_t)gen_state_row_words(m, sw) * 4 * Bz);
     sb->sticky = (int*)take(64);
     sb->ws_bytes = carve(m, B, nullptr, &b, &pl, sw);
@@ -1454,6 +1464,7 @@ int session_open(Session& se, char* arena, size_t arena_bytes) {
     r.noise = sb.noise;
     r.seq = sb.seq;
     r.logp = sb.logp;
+    r.score = sb.score;
     r.workspace = sb.ws;
     r.workspace_bytes = sb.ws_bytes;
     r.temperature = sb.temperature;
@@ -1488,7 +1499,7 @@ int session_open(Session& se, char* arena, size_t arena_bytes) {
 }
 
 // Everything a chunk is refused for, before anything is queued.
-int session_check(const Session& se, const SrnnGenChunk& ck) {
+int session_check(const Session& se, const SrnnGenChunk& ck, const float* score_out) {
     const GenRequest& r = se.rq;
     SRNN_REQUIRE(ck.n_frames >= 1 && ck.n_frames <= se.max_frames,
                  "gen_session: a chunk of %d frames, the session was opened for 1..%d",
@@ -1512,6 +1523,8 @@ int session_check(const Session& se, const SrnnGenChunk& ck) {
                  "for it");
     SRNN_REQUIRE(!ck.logp_out || (se.flags & SRNN_GEN_SESSION_LOGP),
                  "gen_session: log-probs need a session opened for them");
+    SRNN_REQUIRE(!score_out || (se.flags & SRNN_GEN_SESSION_SCORE),
+                 "gen_session: scores need a session opened for them (SRNN_GEN_SESSION_SCORE)");
     if (ck.noise_row)
         for (int b = 0; b < r.n_seqs; ++b)
             SRNN_REQUIRE(ck.noise_row[b] >= 0, "generate: noise_row[%zu] = %d is negative",
@@ -1548,7 +1561,7 @@ int session_block(Session& se, int periods) {
 }
 
 // Queues a checked chunk; every step is ordered on the session's stream.
-int session_queue(Session& se, const SrnnGenChunk& ck, hipStream_t user) {
+int session_queue(Session& se, const SrnnGenChunk& ck, float* score_out, hipStream_t user) {
     Ctx& c = se.c;
     const GenRequest& r = se.rq;
     const SessBufs& sb = se.sb;
@@ -1608,17 +1621,19 @@ int session_queue(Session& se, const SrnnGenChunk& ck, hipStream_t user) {
                                         B, hipMemcpyDefault, s));
     if (ck.logp_out)
         SRNN_CHECK_HIP(hipMemcpyAsync(ck.logp_out, sb.logp, T * B * 256 * 4, hipMemcpyDefault, s));
+    if (score_out)
+        SRNN_CHECK_HIP(hipMemcpyAsync(score_out, sb.score, T * B * 8, hipMemcpyDefault, s));
     RET(gen_rows_err_launch(c.pl ? c.b.gerr : nullptr, sb.sticky, s));
     SRNN_CHECK_HIP(hipMemcpyAsync((void*)se.host_err, sb.sticky, sizeof(int),
                                   hipMemcpyDeviceToHost, s));
     return 0;
 }
 
-int session_chunk(Session& se, const SrnnGenChunk& ck, hipStream_t user) {
+int session_chunk(Session& se, const SrnnGenChunk& ck, float* score_out, hipStream_t user) {
     if (se.poisoned) return se.refused();
     if (*se.host_err) return se.poison_err_word();
-    RET(session_check(se, ck));
-    if (session_queue(se, ck, user)) return se.poison();
+    RET(session_check(se, ck, score_out));
+    if (session_queue(se, ck, score_out, user)) return se.poison();
     const int64_t T = (int64_t)ck.n_frames * se.c.L;
     for (int64_t& v : se.steps) v += T;
     se.st.chunks++;
@@ -1736,7 +1751,15 @@ extern "C" int srnn_gen_session_open(const SrnnModel* m, int n_seqs, int max_fra
 extern "C" int srnn_gen_session_chunk(SrnnGenSession* s, const SrnnGenChunk* chunk,
                                       void* stream) {
     SRNN_REQUIRE(s && chunk, "gen_session: bad args");
-    return session_chunk(*session_of(s), *chunk, (hipStream_t)stream);
+    return session_chunk(*session_of(s), *chunk, nullptr, (hipStream_t)stream);
+}
+
+// srnn_gen_session_chunk that also writes the chunk's score pairs (n_frames L, n_seqs, 2) to
+// score_out (device or pinned memory), as logp_out is written; score_out null: that entry
+extern "C" int srnn_gen_session_chunk2(SrnnGenSession* s, const SrnnGenChunk* chunk,
+                                       float* score_out, void* stream) {
+    SRNN_REQUIRE(s && chunk, "gen_session: bad args");
+    return session_chunk(*session_of(s), *chunk, score_out, (hipStream_t)stream);
 }
 
 extern "C" int srnn_gen_session_sync(SrnnGenSession* s) {
@@ -1781,12 +1804,12 @@ extern "C" int srnn_gen_session_stats(const SrnnGenSession* s, SrnnGenSessionSta
 extern "C" int srnn_gen_session_close(SrnnGenSession* s) { return session_close(session_of(s)); }
 
 // rows per group of the persistent sample loop at sampling-control level `level` (0: the plain
-// plan; 1: temperature / top_k / a forced prefix, 64 B more LDS; 2: with top_p, 96 B more), or
-// 0 where the call would run the per-sample kernels
+// plan; 1: temperature / top_k / a forced prefix, 64 B more LDS; 2: with top_p, 96 B more; 3:
+// level 2 with scores), or 0 where the call would run the per-sample kernels
 extern "C" int srnn_gen_persistent_rows_level(int dtype, int n_seqs, int dim, int fs0,
                                               int q_levels, int level) {
     GenMlpPlan pl;
-    if (level < 0 || level > 2) return 0;
+    if (level < 0 || level > 3) return 0;
     if (!gen_mlp_plan(dtype, n_seqs, dim, fs0, q_levels, level, &pl) ||
         !GenSwitches::read().persist)
         return 0;
@@ -1893,6 +1916,27 @@ extern "C" int srnn_generate6(const SrnnModel* m, int n_seqs, int n_cond, const 
                     workspace_bytes, flags, (hipStream_t)stream, temperature, top_k, top_p,
                     st->state_in, st->state_out, st->state_bytes, rows->step0 ? 0u : st->step0,
                     st->n_forced, rows->noise_row, rows->step0});
+}
+
+// that also writes the steps' score pairs (sampler.hpp row_score) to score (n_cond L, n_seqs, 2):
+// score given selects the scored instantiations (level 3); score null: srnn_generate6, same
+// kernels.
+extern "C" int srnn_generate7(const SrnnModel* m, int n_seqs, int n_cond, const float* cond,
+                              const float* row_bias, const float* noise, uint64_t seed,
+                              int row0, int64_t* seq, float* logp, void* workspace,
+                              size_t workspace_bytes, int flags, void* stream,
+                              const float* temperature, const int32_t* top_k,
+                              const float* top_p, const SrnnGenStream* st,
+                              const SrnnGenRows* rows, float* score) {
+    static const SrnnGenStream none{};
+    static const SrnnGenRows norows{};
+    if (!st) st = &none;
+    if (!rows) rows = &norows;
+    SRNN_REQUIRE(((uintptr_t)score & 7) == 0, "generate: score must be 8-byte aligned");
+    return gen_run({m, n_seqs, n_cond, cond, row_bias, noise, seed, row0, seq, logp, workspace,
+                    workspace_bytes, flags, (hipStream_t)stream, temperature, top_k, top_p,
+                    st->state_in, st->state_out, st->state_bytes, rows->step0 ? 0u : st->step0,
+                    st->n_forced, rows->noise_row, rows->step0, score});
 }
 
 // n_seqs records of a stream that has done no step, as a fresh start of n_seqs rows computes

@@ -649,11 +649,49 @@ __global__ __launch_bounds__(256) void sample_kernel(
     if (lane == 0) seq[(int64_t)b * ldseq + i] = bi;
 }
 
+// The scored build (level 3) of sample_kernel, a kernel of its own so that the ones above keep
+// their signature: the level-2 draw, then the score pair of the step's sample -- the forced
+// one at a forced step -- and the dense row, if asked, from one pass (sampler.hpp row_score).
+__global__ __launch_bounds__(256) void sample_scored_kernel(
+    const float* __restrict__ z, int64_t ldz, int B, const float* __restrict__ noise,
+    uint64_t seed, int row0, const int* __restrict__ base, int off, int L,
+    int64_t* __restrict__ seq, int64_t ldseq, float* __restrict__ logp_out,
+    const float* __restrict__ temperature, const int* __restrict__ top_k,
+    const float* __restrict__ top_p, uint32_t step0, const int* __restrict__ n_forced,
+    float* __restrict__ score) {
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (b >= B) return;
+    const int i = *base + off;
+    const int step = i - L;
+    const floatx4 v = *reinterpret_cast<const floatx4*>(z + (int64_t)b * ldz + 4 * lane);
+    const floatx4 lq = log_noise(sample_noise(noise, seed, B, b, step, lane, row0, step0));
+    float* lrow = logp_out ? logp_out + ((int64_t)step * B + b) * 256 : nullptr;
+    floatx4 zz;
+    int bi = sample_row_ctrl_z(v, lq, temperature ? temperature[b] : 1.0f, top_k ? top_k[b] : 0,
+                               top_p ? top_p[b] : 1.0f, zz, lane);
+    const bool forced = n_forced && step < n_forced[b];
+    if (forced) bi = (int)seq[(int64_t)b * ldseq + i] & 255;
+    const float2 sc = row_score(zz, bi, lrow, lane);
+    if (lane == 0) {
+        *reinterpret_cast<float2*>(score + ((int64_t)step * B + b) * 2) = sc;
+        if (!forced) seq[(int64_t)b * ldseq + i] = bi;
+    }
+}
+
 int srnn_sample_impl(const float* z, int64_t ldz, int B, const float* noise, uint64_t seed,
                      int row0, const int* base, int off, int L, int64_t* seq, int64_t ldseq,
                      float* logp_out, const float* temperature, const int* top_k,
-                     const float* top_p, uint32_t step0, const int* n_forced, hipStream_t s) {
-    const int lv = sample_ctrl_level(temperature, top_k, top_p, n_forced);
+                     const float* top_p, uint32_t step0, const int* n_forced, float* score,
+                     hipStream_t s) {
+    const int lv = sample_ctrl_level(temperature, top_k, top_p, n_forced, score);
+    if (lv == 3) {
+        hipLaunchKernelGGL(sample_scored_kernel, dim3(cdiv(B, 4)), dim3(256), 0, s, z, ldz, B,
+                           noise, seed, row0, base, off, L, seq, ldseq, logp_out, temperature,
+                           top_k, top_p, step0, n_forced, score);
+        SRNN_LAUNCH_CHECK();
+        return 0;
+    }
     auto k = lv == 2 ? sample_kernel<2> : lv == 1 ? sample_kernel<1> : sample_kernel<0>;
     hipLaunchKernelGGL(k, dim3(cdiv(B, 4)), dim3(256), 0, s, z, ldz, B, noise, seed, row0, base,
                        off, L, seq, ldseq, logp_out, temperature, top_k, top_p, step0, n_forced);
@@ -681,21 +719,61 @@ __global__ __launch_bounds__(256) void sample_rows_kernel(
     if (lane == 0) idx[b] = bi;
 }
 
-extern "C" int srnn_sample_rows(const float* logits, int64_t ld, int rows, const float* noise,
-                                uint64_t seed, int row0, int step, const float* temperature,
-                                const int32_t* top_k, const float* top_p, int64_t* index,
-                                float* logp, void* stream) {
+// its scored build (level 3), as sample_scored_kernel
+__global__ __launch_bounds__(256) void sample_rows_scored_kernel(
+    const float* __restrict__ z, int64_t ldz, int B, const float* __restrict__ noise,
+    uint64_t seed, int row0, int step, int64_t* __restrict__ idx, float* __restrict__ logp_out,
+    const float* __restrict__ temperature, const int* __restrict__ top_k,
+    const float* __restrict__ top_p, float* __restrict__ score) {
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (b >= B) return;
+    const floatx4 v = *reinterpret_cast<const floatx4*>(z + (int64_t)b * ldz + 4 * lane);
+    const floatx4 lq = log_noise(sample_noise(noise, seed, B, b, noise ? 0 : step, lane, row0));
+    float* lrow = logp_out ? logp_out + (int64_t)b * 256 : nullptr;
+    floatx4 zz;
+    const int bi = sample_row_ctrl_z(v, lq, temperature ? temperature[b] : 1.0f,
+                                     top_k ? top_k[b] : 0, top_p ? top_p[b] : 1.0f, zz, lane);
+    const float2 sc = row_score(zz, bi, lrow, lane);
+    if (lane == 0) {
+        idx[b] = bi;
+        *reinterpret_cast<float2*>(score + (int64_t)b * 2) = sc;
+    }
+}
+
+// srnn_sample_rows with the rows' score pairs (rows, 2) (sampler.hpp row_score): score given
+// selects the scored instantiation; null launches exactly what srnn_sample_rows launches
+extern "C" int srnn_sample_rows2(const float* logits, int64_t ld, int rows, const float* noise,
+                                 uint64_t seed, int row0, int step, const float* temperature,
+                                 const int32_t* top_k, const float* top_p, int64_t* index,
+                                 float* logp, void* stream, float* score) {
     SRNN_REQUIRE(logits && index && rows > 0, "sample_rows: bad args");
     SRNN_REQUIRE(ld >= 256 && ld % 4 == 0 && ((uintptr_t)logits & 15) == 0,
                  "sample_rows: logits rows must be 16-byte aligned (ld %lld)", (long long)ld);
     SRNN_REQUIRE(((uintptr_t)noise & 15) == 0, "sample_rows: noise must be 16-byte aligned");
     SRNN_REQUIRE(row0 >= 0 && step >= 0, "sample_rows: negative row offset or step");
-    const int lv = sample_ctrl_level(temperature, top_k, top_p);
+    SRNN_REQUIRE(((uintptr_t)score & 7) == 0, "sample_rows: score must be 8-byte aligned");
+    const int lv = sample_ctrl_level(temperature, top_k, top_p, nullptr, score);
+    if (lv == 3) {
+        hipLaunchKernelGGL(sample_rows_scored_kernel, dim3(cdiv(rows, 4)), dim3(256), 0,
+                           (hipStream_t)stream, logits, ld, rows, noise, seed, row0, step, index,
+                           logp, temperature, top_k, top_p, score);
+        SRNN_LAUNCH_CHECK();
+        return 0;
+    }
     auto k = lv == 2 ? sample_rows_kernel<2> : lv == 1 ? sample_rows_kernel<1>
                                                        : sample_rows_kernel<0>;
     hipLaunchKernelGGL(k, dim3(cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, logits, ld, rows,
                        noise, seed, row0, step, index, logp, temperature, top_k, top_p);
     SRNN_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int srnn_sample_rows(const float* logits, int64_t ld, int rows, const float* noise,
+                                uint64_t seed, int row0, int step, const float* temperature,
+                                const int32_t* top_k, const float* top_p, int64_t* index,
+                                float* logp, void* stream) {
+    return srnn_sample_rows2(logits, ld, rows, noise, seed, row0, step, temperature, top_k, top_p,
+                             index, logp, stream, nullptr);
 }
 

@@ -140,6 +140,43 @@ __device__ __forceinline__ void row_logp(const floatx4& v, float* logp_row, int 
     for (int j = 0; j < 4; ++j) logp_row[4 * lane + j] = (v[j] - m) - ls;
 }
 
+// The step's score pair of a row: {log-prob of the step's sample x, entropy of softmax(z)} in
+// nats, both of the model's own distribution whatever the controls did to the draw; x is the
+// index drawn, or the caller's sample at a forced step (wave-uniform).  Operation order, the
+// same in every kernel (the per-sample kernels and the persistent loop give identical bits):
+//   m = wave_max z;  d_j = z_j - m;  e_j = expf(d_j);  s = wave_sum(((e_0 + e_1) + e_2) + e_3);
+//   ls = logf(s)                                        -- row_logp's operations in its order
+//   score.x = (z_x - m) - ls                            -- row_logp's logp_row[x], bit for bit:
+//             computed in every lane for j = x & 3, read from lane x >> 2
+//   u = wave_sum(fma(e_3, d_3, fma(e_2, d_2, fma(e_1, d_1, fma(e_0, d_0, 0)))))
+//             (a term with e_j == 0 is 0, also at z_j = -inf)
+//   score.y = fmaxf(0, ls - u / s)
+// logp_row non-null: the dense row as well, from the same m and ls.
+__device__ __forceinline__ float2 row_score(const floatx4& v, int x, float* logp_row, int lane) {
+    x = __builtin_amdgcn_readfirstlane(x);
+    float m = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
+    m = wave_max(m);
+    float s = 0.f, u = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float d = v[j] - m, e = expf(d);
+        s += e;
+        u = __builtin_fmaf(e, e > 0.f ? d : 0.f, u);
+    }
+    s = wave_sum(s);
+    u = wave_sum(u);
+    const float ls = logf(s);
+    const int jx = x & 3;
+    const float zx = jx == 0 ? v[0] : jx == 1 ? v[1] : jx == 2 ? v[2] : v[3];
+    const float lpx = __uint_as_float(
+        (uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint((zx - m) - ls), x >> 2));
+    if (logp_row) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) logp_row[4 * lane + j] = (v[j] - m) - ls;
+    }
+    return make_float2(lpx, fmaxf(0.f, ls - u / s));
+}
+
 // One wave, one row of Q = 256 logits (lane holds q = 4 lane + j), lq = log_noise(q).
 // Returns the sampled index (wave-uniform); writes the row's log-probs to logp_row (if
 // non-null).  The draw argmax_j softmax(z)_j / q_j (model.py:514) is taken in log space as
@@ -303,14 +340,14 @@ __device__ __forceinline__ uint32_t wave_nucleus_key(const uint32_t (&key)[4], f
 // the row held as keys in place of the logits; each is skipped by a wave-uniform branch when
 // its control is off, and with p off the draw is sample_row_ctrl(v, lq, tau, k)'s, bit for bit.
 // tau <= 0 (greedy) ignores p.  The allowed set is the float compare z_j >= max(v_k, v_p).
-__device__ __forceinline__ int sample_row_ctrl(const floatx4& v, const floatx4& lq, float tau,
-                                               int k, float p, float* logp_row, int lane) {
+__device__ __forceinline__ int sample_row_ctrl_z(const floatx4& v, const floatx4& lq, float tau,
+                                                 int k, float p, floatx4& z, int lane) {
     tau = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(tau)));
     k = __builtin_amdgcn_readfirstlane(k);
     p = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(p)));
     const bool ksel = k >= 1 && k <= 255;
     const bool psel = p > 0.f && p < 1.f && tau > 0.f;
-    floatx4 z = v;
+    z = v;
     float vk = -__builtin_inff();
     if (ksel || psel) {
         uint32_t key[4];
@@ -330,16 +367,23 @@ __device__ __forceinline__ int sample_row_ctrl(const floatx4& v, const floatx4& 
         const float sc = tau > 0.f ? __builtin_fmaf(-tau, lq[j], z[j]) : z[j];
         t[j] = z[j] >= vk ? sc : -__builtin_inff();
     }
-    const int bi = row_argmax(t, lane);
+    return row_argmax(t, lane);
+}
+__device__ __forceinline__ int sample_row_ctrl(const floatx4& v, const floatx4& lq, float tau,
+                                               int k, float p, float* logp_row, int lane) {
+    floatx4 z;
+    const int bi = sample_row_ctrl_z(v, lq, tau, k, p, z, lane);
     if (logp_row) row_logp(z, logp_row, lane);
     return bi;
 }
 
-// The level of a call's sampling controls, from the arrays it was given: 2 with top_p, 1 with
-// temperature, top_k or a forced prefix (n_forced: the controlled builds keep it), else 0.
+// The level of a call's sampling controls, from the arrays it was given: 3 with a score buffer
+// (level 2 plus row_score: default controls draw the plain stream, so the one scored build
+// serves every call), 2 with top_p, 1 with temperature, top_k or a forced prefix (n_forced: the
+// controlled builds keep it), else 0.
 // The one definition: it picks the samplers' instantiation (CT), the persistent loop's plan
 // and its launch check.
 inline int sample_ctrl_level(const void* temperature, const void* top_k, const void* top_p,
-                             const void* n_forced = nullptr) {
-    return top_p ? 2 : (temperature || top_k || n_forced) ? 1 : 0;
+                             const void* n_forced = nullptr, const void* score = nullptr) {
+    return score ? 3 : top_p ? 2 : (temperature || top_k || n_forced) ? 1 : 0;
 }

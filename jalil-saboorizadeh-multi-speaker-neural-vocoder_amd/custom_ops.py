@@ -19,6 +19,10 @@ The drop-in classes call these ops, so the registered ops ARE the product path:
   srnn::generate_stream         the loop over a chunk of a stream: carried state in / out, a
                                 Philox step origin, a forced prefix; optional controls
   srnn::sample_rows             the loops' row sampler on caller-chosen logits
+  srnn::generate_scored         srnn::generate_rows that also returns every step's score pair
+                                (log-prob of the step's sample, entropy of the softmax)
+  srnn::sample_rows_scored      srnn::sample_rows with the rows' score pairs
+  srnn::gen_session_chunk_scored  a chunk of a session opened for scores, with its score pairs
   srnn::gen_session_chunk       one chunk of a generation session (model.GenSession): the loop
                                 from the session's kept weights, workspace, records and graph
   srnn::gen_session_state       the session's records
@@ -408,12 +412,14 @@ def _(dstep):
 # ------------------------------------------------------------------ generation
 def _generate(weights, meta, cond, row_bias, noise, seed, row_offset, flags, return_logp,
               temperature=None, top_k=None, top_p=None, state=None, step0=0, prefix=None,
-              n_forced=None, return_state=False, noise_row=None, row_step0=None):
-    """The one path into the library's generation (srnn_generate6), behind the five registered
-    ops, which check their arguments first: allocates seq (q_zero history, the prefix written
-    in), logp, the end state and the workspace, fills SrnnGenStream and SrnnGenRows and calls.
-    Everything at its default launches the plain kernels.  Returns (seq, logp, end state or
-    empty)."""
+              n_forced=None, return_state=False, noise_row=None, row_step0=None,
+              return_scores=False):
+    """The one path into the library's generation (srnn_generate6; srnn_generate7 with
+    return_scores), behind the registered ops, which check their arguments first: allocates seq
+    (q_zero history, the prefix written in), logp, the end state and the workspace, fills
+    SrnnGenStream and SrnnGenRows and calls.  Everything at its default launches the plain
+    kernels.  Returns (seq, logp, end state or empty), with return_scores also the (T, n_seqs,
+    2) score pairs."""
     import ctypes
     import model
     m = model.srnn_model_struct(weights, meta)
@@ -442,11 +448,16 @@ def _generate(weights, meta, cond, row_bias, noise, seed, row_offset, flags, ret
     H.lib().call('srnn_gen_workspace_size', ctypes.byref(m), n_seqs, ctypes.byref(sz))
     ws = torch.empty(sz.value, device=dev, dtype=torch.uint8)
     rows = H.SrnnGenRows(H.ptr(noise_row), H.ptr(row_step0))
-    H.lib().call('srnn_generate6', ctypes.byref(m), n_seqs, num_cond, H.ptr(cond),
-                 H.ptr(row_bias), H.ptr(noise), int(seed) & ((1 << 64) - 1), int(row_offset),
-                 H.ptr(seq), H.ptr(logp) if return_logp else None, H.ptr(ws), sz.value, int(flags),
-                 H.stream(), H.ptr(temperature), H.ptr(top_k), H.ptr(top_p), ctypes.byref(st),
-                 ctypes.byref(rows) if noise_row is not None or row_step0 is not None else None)
+    args = (ctypes.byref(m), n_seqs, num_cond, H.ptr(cond),
+            H.ptr(row_bias), H.ptr(noise), int(seed) & ((1 << 64) - 1), int(row_offset),
+            H.ptr(seq), H.ptr(logp) if return_logp else None, H.ptr(ws), sz.value, int(flags),
+            H.stream(), H.ptr(temperature), H.ptr(top_k), H.ptr(top_p), ctypes.byref(st),
+            ctypes.byref(rows) if noise_row is not None or row_step0 is not None else None)
+    if return_scores:
+        score = torch.empty((T, n_seqs, 2), device=dev)
+        H.lib().call('srnn_generate7', *args, H.ptr(score))
+        return seq, logp, out_state, score
+    H.lib().call('srnn_generate6', *args)
     return seq, logp, out_state
 
 
@@ -569,8 +580,9 @@ def generate_stream(weights: list[Tensor], meta: list[int], cond: Tensor, row_bi
 
 def _generate_stream(op, weights, meta, cond, row_bias, noise, seed, row_offset, flags,
                      return_logp, temperature, top_k, top_p, state, step0, prefix, prefix_len,
-                     return_state, noise_row=None, row_step0=None):
-    """The argument checks and the call of srnn::generate_stream and srnn::generate_rows."""
+                     return_state, noise_row=None, row_step0=None, return_scores=False):
+    """The argument checks and the call of srnn::generate_stream, srnn::generate_rows and
+    srnn::generate_scored."""
     n_seqs, dev = cond.shape[0], cond.device
     T = cond.shape[1] * meta[-1]            # steps of the call (meta: _generate_fake)
     ctl = [(n, t, dt) for n, t, dt in (('temperature', temperature, torch.float32),
@@ -613,7 +625,7 @@ def _generate_stream(op, weights, meta, cond, row_bias, noise, seed, row_offset,
         state = state.contiguous()
     return _generate(weights, meta, cond, row_bias, noise, seed, row_offset, flags, return_logp,
                      temperature, top_k, top_p, state, step0, prefix, n_forced, return_state,
-                     noise_row, row_step0)
+                     noise_row, row_step0, return_scores)
 
 
 @generate_stream.register_fake
@@ -652,6 +664,33 @@ def _(weights, meta, cond, row_bias, noise, seed, row_offset, flags, return_logp
     return seq, logp, cond.new_empty(rows, dtype=torch.uint8)
 
 
+@torch.library.custom_op('srnn::generate_scored', mutates_args=())
+def generate_scored(weights: list[Tensor], meta: list[int], cond: Tensor, row_bias: Tensor,
+                    noise: Optional[Tensor], seed: int, row_offset: int, flags: int,
+                    return_logp: bool, temperature: Optional[Tensor], top_k: Optional[Tensor],
+                    top_p: Optional[Tensor], state: Optional[Tensor], step0: int,
+                    prefix: Optional[Tensor], prefix_len: Optional[Tensor], return_state: bool,
+                    noise_row: Optional[Tensor],
+                    row_step0: Optional[Tensor]) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+    """srnn::generate_rows that also returns every step's score pair (srnn_generate7): the
+    fourth result is (T, n_seqs, 2) float32, [..., 0] the log-prob of the step's sample (the
+    forced one at a forced step; the dense logp gathered there, bit for bit) and [..., 1] the
+    entropy of the model's softmax in nats, both whatever the controls did to the draw.  Runs
+    the samplers' scored builds (level 3); the index stream is srnn::generate_rows'."""
+    return _generate_stream('generate_scored', weights, meta, cond, row_bias, noise, seed,
+                            row_offset, flags, return_logp, temperature, top_k, top_p, state, step0,
+                            prefix, prefix_len, return_state, noise_row, row_step0, True)
+
+
+@generate_scored.register_fake
+def _(weights, meta, cond, row_bias, noise, seed, row_offset, flags, return_logp, temperature,
+      top_k, top_p, state, step0, prefix, prefix_len, return_state, noise_row, row_step0):
+    seq, logp = _generate_fake(meta, cond, return_logp)
+    rows = (cond.shape[0], gen_state_row_bytes(meta)) if return_state else (0,)
+    return (seq, logp, cond.new_empty(rows, dtype=torch.uint8),
+            cond.new_empty((cond.shape[1] * meta[-1], cond.shape[0], 2)))
+
+
 @torch.library.custom_op('srnn::gen_state_fresh', mutates_args=())
 def gen_state_fresh(weights: list[Tensor], meta: list[int], n_seqs: int) -> Tensor:
     """(n_seqs, row_bytes) uint8 records of rows that have done no step (srnn_gen_state_fresh):
@@ -683,8 +722,11 @@ def gen_session_open(weights, meta, n_seqs, max_frames, level, seed, row_offset,
     alive, and unchanged, until gen_session_close(handle) -- the session reads both."""
     import ctypes
     import model
-    if n_seqs < 1 or max_frames < 1 or level not in (0, 1, 2):
-        raise ValueError('gen_session_open: n_seqs and max_frames must be >= 1, level 0, 1 or 2')
+    if n_seqs < 1 or max_frames < 1 or level not in (0, 1, 2, 3):
+        raise ValueError('gen_session_open: n_seqs and max_frames must be >= 1, level 0, 1, 2 '
+                         'or 3')
+    if (level == 3) != bool(flags & H.GEN_SESSION_SCORE):
+        raise ValueError('gen_session_open: level 3 and GEN_SESSION_SCORE go together')
     m = model.srnn_model_struct(weights, meta)
     dev = weights[0].device
     sz = ctypes.c_size_t(0)
@@ -725,8 +767,15 @@ def gen_session_chunk(handle: int, lookback: int, cond: Tensor, row_bias: Option
     (T, n_seqs, 256) float32 for a session opened for replayed noise.  Returns (the chunk's
     sample indices (n_seqs, T) int64, log-probs (T, n_seqs, 256) or empty), T = frames *
     lookback.  The library checks the chunk against the session before it queues anything."""
+    return _gen_session_chunk('gen_session_chunk', handle, lookback, cond, row_bias, temperature,
+                              top_k, top_p, prefix, prefix_len, noise_row, noise, return_logp,
+                              False)
+
+
+def _gen_session_chunk(op, handle, lookback, cond, row_bias, temperature, top_k, top_p, prefix,
+                       prefix_len, noise_row, noise, return_logp, return_scores):
+    """The argument checks and the call of srnn::gen_session_chunk and its scored twin."""
     import ctypes
-    op = 'gen_session_chunk'
     if (cond.dim() != 3 or cond.dtype != torch.float32 or not cond.is_cuda or
             not cond.is_contiguous()):
         raise ValueError(op + ': cond must be a contiguous (n_seqs, frames, C) float32 device '
@@ -769,6 +818,12 @@ def gen_session_chunk(handle: int, lookback: int, cond: Tensor, row_bias: Option
     ck.temperature, ck.top_k, ck.top_p = H.ptr(temperature), H.ptr(top_k), H.ptr(top_p)
     ck.noise_row, ck.noise = H.ptr(noise_row), H.ptr(noise)
     ck.seq_out, ck.logp_out = H.ptr(seq), H.ptr(logp) if return_logp else None
+    if return_scores:
+        score = torch.empty((T, n_seqs, 2), device=dev)
+        H.lib().call('srnn_gen_session_chunk2', handle, ctypes.byref(ck), H.ptr(score),
+                     H.stream())
+        H.lib().call('srnn_gen_session_sync', handle)
+        return seq, logp, score
     H.lib().call('srnn_gen_session_chunk', handle, ctypes.byref(ck), H.stream())
     H.lib().call('srnn_gen_session_sync', handle)
     return seq, logp
@@ -780,6 +835,30 @@ def _(handle, lookback, cond, row_bias, temperature, top_k, top_p, prefix, prefi
     n_seqs, T = cond.shape[0], cond.shape[1] * lookback
     return (cond.new_empty((n_seqs, T), dtype=torch.long),
             cond.new_empty((T, n_seqs, 256) if return_logp else (0,)))
+
+
+@torch.library.custom_op('srnn::gen_session_chunk_scored', mutates_args=())
+def gen_session_chunk_scored(handle: int, lookback: int, cond: Tensor,
+                             row_bias: Optional[Tensor], temperature: Optional[Tensor],
+                             top_k: Optional[Tensor], top_p: Optional[Tensor],
+                             prefix: Optional[Tensor], prefix_len: Optional[Tensor],
+                             noise_row: Optional[Tensor], noise: Optional[Tensor],
+                             return_logp: bool) -> tuple[Tensor, Tensor, Tensor]:
+    """srnn::gen_session_chunk of a session opened for scores (srnn_gen_session_chunk2): also
+    returns the chunk's (T, n_seqs, 2) score pairs, srnn::generate_scored's.  The library
+    refuses it, with nothing queued, on a session opened without GEN_SESSION_SCORE."""
+    return _gen_session_chunk('gen_session_chunk_scored', handle, lookback, cond, row_bias,
+                              temperature, top_k, top_p, prefix, prefix_len, noise_row, noise,
+                              return_logp, True)
+
+
+@gen_session_chunk_scored.register_fake
+def _(handle, lookback, cond, row_bias, temperature, top_k, top_p, prefix, prefix_len, noise_row,
+      noise, return_logp):
+    n_seqs, T = cond.shape[0], cond.shape[1] * lookback
+    return (cond.new_empty((n_seqs, T), dtype=torch.long),
+            cond.new_empty((T, n_seqs, 256) if return_logp else (0,)),
+            cond.new_empty((T, n_seqs, 2)))
 
 
 @torch.library.custom_op('srnn::gen_session_state', mutates_args=())
@@ -820,6 +899,13 @@ def sample_rows(logits: Tensor, noise: Optional[Tensor], seed: int, row0: int, s
     log_softmax(logits) or empty).  noise (rows, 256) float32 Exp(1) or None = Philox with
     (seed, row0, step); temperature / top_k / top_p (rows,) float32 / int32 / float32 or None,
     at whose level the draw runs (all None: the plain draw)."""
+    return _sample_rows(logits, noise, seed, row0, step, temperature, top_k, top_p, return_logp,
+                        False)
+
+
+def _sample_rows(logits, noise, seed, row0, step, temperature, top_k, top_p, return_logp,
+                 return_scores):
+    """The argument checks and the call of srnn::sample_rows and srnn::sample_rows_scored."""
     if (logits.dim() != 2 or logits.shape[1] != 256 or logits.dtype != torch.float32 or
             not logits.is_cuda or logits.stride(1) != 1 or logits.shape[0] < 1):
         raise ValueError('sample_rows: logits must be a (rows, 256) float32 device tensor with '
@@ -839,10 +925,15 @@ def sample_rows(logits: Tensor, noise: Optional[Tensor], seed: int, row0: int, s
                                               ('top_p', top_p, torch.float32)) if t is not None])
     idx = torch.empty(rows, device=dev, dtype=torch.int64)
     logp = torch.empty((rows, 256) if return_logp else (0,), device=dev, dtype=torch.float32)
-    H.lib().call('srnn_sample_rows', H.ptr(logits), logits.stride(0) if rows > 1 else 256, rows,
-                 H.ptr(noise), int(seed) & ((1 << 64) - 1), int(row0), int(step),
-                 H.ptr(temperature), H.ptr(top_k), H.ptr(top_p), H.ptr(idx),
-                 H.ptr(logp) if return_logp else None, H.stream())
+    args = (H.ptr(logits), logits.stride(0) if rows > 1 else 256, rows,
+            H.ptr(noise), int(seed) & ((1 << 64) - 1), int(row0), int(step),
+            H.ptr(temperature), H.ptr(top_k), H.ptr(top_p), H.ptr(idx),
+            H.ptr(logp) if return_logp else None, H.stream())
+    if return_scores:
+        score = torch.empty((rows, 2), device=dev, dtype=torch.float32)
+        H.lib().call('srnn_sample_rows2', *args, H.ptr(score))
+        return idx, logp, score
+    H.lib().call('srnn_sample_rows', *args)
     return idx, logp
 
 
@@ -853,7 +944,29 @@ def _(logits, noise, seed, row0, step, temperature, top_k, top_p, return_logp):
             logits.new_empty((rows, 256) if return_logp else (0,)))
 
 
+@torch.library.custom_op('srnn::sample_rows_scored', mutates_args=())
+def sample_rows_scored(logits: Tensor, noise: Optional[Tensor], seed: int, row0: int, step: int,
+                       temperature: Optional[Tensor], top_k: Optional[Tensor],
+                       top_p: Optional[Tensor],
+                       return_logp: bool) -> tuple[Tensor, Tensor, Tensor]:
+    """srnn::sample_rows that also returns the rows' (rows, 2) float32 score pairs
+    (srnn_sample_rows2): the log-prob of the index drawn (logp gathered there, bit for bit) and
+    the entropy of softmax(logits) in nats, whatever the controls.  The draw is the scored
+    build's (level 3), which draws srnn::sample_rows' index."""
+    return _sample_rows(logits, noise, seed, row0, step, temperature, top_k, top_p, return_logp,
+                        True)
+
+
+@sample_rows_scored.register_fake
+def _(logits, noise, seed, row0, step, temperature, top_k, top_p, return_logp):
+    rows = logits.shape[0]
+    return (logits.new_empty((rows,), dtype=torch.int64),
+            logits.new_empty((rows, 256) if return_logp else (0,)),
+            logits.new_empty((rows, 2)))
+
+
 OPS = ('tier_fwd', 'tier_bwd', 'mlp_fwd', 'mlp_bwd', 'nll_bits', 'nll_bits_bwd', 'upsample',
        'upsample_bwd', 'dequant', 'adam_clip_', 'step_advance_', 'generate', 'generate_ctrl',
        'generate_ctrl_p', 'generate_stream', 'generate_rows', 'gen_state_fresh', 'sample_rows',
-       'gen_session_chunk', 'gen_session_state')
+       'gen_session_chunk', 'gen_session_state', 'generate_scored', 'sample_rows_scored',
+       'gen_session_chunk_scored')

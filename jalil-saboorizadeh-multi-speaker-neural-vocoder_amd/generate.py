@@ -28,6 +28,10 @@ WAV, byte for byte, with the sampler's host noise bounded by the chunk (single-p
 rank-sharded batches are generated whole).
 --session True (with --chunk_frames, or with --batch_files True --slots) runs those chunks through
 one generation session (Generator.session): the same WAVs, without each call's set-up.
+--scores True (default off: the WAVs are byte for byte what they are without it) also writes
+<wav name minus .wav>.scores.npy beside each WAV -- float32 (T, 2), T the file's own length: the
+log-prob of each sample drawn and the entropy of the model's distribution there, in nats -- and
+prints the file's bits per sample.  Rank-sharded batches are generated without scores.
 """
 import argparse
 import os
@@ -39,7 +43,7 @@ import numpy as np
 import torch
 
 from dataset import read_conditioners, write_wav
-from model import Generator, Predictor, SampleRNN, shard_generate
+from model import Generator, Predictor, SampleRNN, bits_per_sample, shard_generate
 
 default_params = {
     # model parameters
@@ -78,16 +82,31 @@ default_params = {
     'chunk_frames': 0,
     'slots': 0,
     'session': False,
+    'scores': False,
 }
 
 
-def run_generator(gen, n_seqs, sample_length, cond, spk, chunk_frames, session=False, **kw):
+def run_generator(gen, n_seqs, sample_length, cond, spk, chunk_frames, session=False,
+                  scores=False, **kw):
     """Generator.__call__, or the concatenated blocks of Generator.stream when chunk_frames is
-    set (equal bit for bit), through one session when asked."""
+    set (equal bit for bit), through one session when asked.  scores: returns (samples, the
+    (n_seqs, T, 2) per-step scores) in place of the samples."""
+    if scores:
+        kw['return_scores'] = True
     if chunk_frames > 0:
-        return torch.cat(list(gen.stream(n_seqs, cond, spk, chunk_frames, session=session,
-                                         **kw)), dim=1)
+        blocks = list(gen.stream(n_seqs, cond, spk, chunk_frames, session=session, **kw))
+        if scores:
+            return tuple(torch.cat([b[k] for b in blocks], dim=1) for k in (0, 1))
+        return torch.cat(blocks, dim=1)
     return gen(n_seqs, sample_length, cond, spk, **kw)
+
+
+def write_scores(wav_name, scores):
+    """The (T, 2) float32 scores of one WAV beside it (<name minus .wav>.scores.npy), and its
+    bits per sample on stdout."""
+    scores = np.ascontiguousarray(np.asarray(scores, dtype=np.float32))
+    np.save(wav_name[:-4] + '.scores.npy', scores)
+    print('%s: %.4f bits per sample' % (wav_name, float(bits_per_sample(scores)[0])))
 
 
 def init_random_seed(seed, cuda):
@@ -216,15 +235,28 @@ def main(frame_sizes, **params):
         gen = Generator(model, use_cuda)
         ctrl = dict(temperature=params['temperature'], top_k=params['top_k'],
                     top_p=params['top_p'])
+        want_scores = params['scores']
+        sc = None
+        if want_scores and world > 1:
+            print('--scores: rank-sharded batches are generated without scores')
+            want_scores = False
         if params['slots'] > 0:
             # stream ids j n + i: the Philox rows of the padded batch below
             given = {k: v for k, v in ctrl.items() if v != default_params[k]}
             reqs = [dict(cond=conds[j], spk=jobs[j][1], stream_id=j * n + i, **given)
                     for j in range(len(jobs)) for i in range(n)]
             out = np.zeros((len(rows), n_cond * model.lookback), dtype=np.float32)
-            for u, samples in gen.serve(reqs, params['slots'], params['chunk_frames'] or 32,
-                                        seed=params['seed'], session=params['session']):
-                out[u, :samples.shape[0]] = samples.numpy()
+            if want_scores:
+                sc = np.zeros((len(rows), n_cond * model.lookback, 2), dtype=np.float32)
+                for u, samples, s in gen.serve(reqs, params['slots'],
+                                               params['chunk_frames'] or 32, seed=params['seed'],
+                                               session=params['session'], scores=True):
+                    out[u, :samples.shape[0]] = samples.numpy()
+                    sc[u, :s.shape[0]] = s.numpy()
+            else:
+                for u, samples in gen.serve(reqs, params['slots'], params['chunk_frames'] or 32,
+                                            seed=params['seed'], session=params['session']):
+                    out[u, :samples.shape[0]] = samples.numpy()
         elif world > 1:
             # rank-sharded: contiguous row shards gathered at the end (rows
             # padded to a multiple of the world size); either sampler reproduces the
@@ -238,7 +270,11 @@ def main(frame_sizes, **params):
         else:
             out = run_generator(gen, len(rows), params['sample_length'], rows, spks,
                                 params['chunk_frames'], session=params['session'],
-                                sampler=params['sampler'], seed=params['seed'], **ctrl).numpy()
+                                scores=want_scores, sampler=params['sampler'],
+                                seed=params['seed'], **ctrl)
+            if want_scores:
+                out, sc = out[0], out[1].numpy()
+            out = out.numpy()
         if rank != 0:
             return
         L = model.lookback
@@ -246,6 +282,8 @@ def main(frame_sizes, **params):
             fname = output_name(params['model'], original, str(spk[sp]))
             for i in range(n):
                 write_wav(fname, out[j * n + i, :conds[j].shape[0] * L], sr=params['sample_rate'])
+                if sc is not None:
+                    write_scores(fname, sc[j * n + i, :conds[j].shape[0] * L])
         return
     for j, (stem, speaker, original) in enumerate(jobs):
         if j % world != rank:       # files are independent: round-robin over the ranks
@@ -258,11 +296,18 @@ def main(frame_sizes, **params):
         gen = Generator(model, use_cuda)
         samples = run_generator(gen, params['n_samples'], params['sample_length'], cond, speaker,
                                 params['chunk_frames'], session=params['session'],
+                                scores=params['scores'],
                                 sampler=params['sampler'], seed=params['seed'],
                                 temperature=params['temperature'],
-                                top_k=params['top_k'], top_p=params['top_p']).numpy()
+                                top_k=params['top_k'], top_p=params['top_p'])
+        sc = None
+        if params['scores']:
+            samples, sc = samples
+        samples = samples.numpy()
         for i in range(params['n_samples']):
             write_wav(fname, samples[i, :], sr=params['sample_rate'])
+            if sc is not None:
+                write_scores(fname, sc[i].numpy())
 
 
 def parse_bool(arg):
@@ -290,7 +335,8 @@ def build_parser():
                       ('cond_list', str), ('spk_list', str), ('sampler', str),
                       ('batch_files', parse_bool), ('compute_dtype', str),
                       ('temperature', float), ('top_k', int), ('top_p', float),
-                      ('chunk_frames', int), ('slots', int), ('session', parse_bool)):
+                      ('chunk_frames', int), ('slots', int), ('session', parse_bool),
+                      ('scores', parse_bool)):
         p.add_argument('--' + name, type=typ)
     # gen.sh passes --results_path (generate.py has no such option; accepted and ignored)
     p.add_argument('--results_path', type=str)

@@ -21,6 +21,7 @@ Numerics: fp32 by default (parity mode, logits within 1e-4 of the reference);
 matmuls on bf16 MFMA with fp32 accumulation, fp32 master weights and fp32 recurrences.
 """
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -1245,6 +1246,33 @@ def forced_prefix(model, n_seqs, T, prefix, prefix_len):
     return p, torch.from_numpy(a.astype(np.int32))
 
 
+def bits_per_sample(scores, lengths=None):
+    """Bits per sample of scored audio: -mean(scores[..., 0]) / ln 2 per row, for the (n_seqs, T,
+    2) scores of Generator.score or of a return_scores call (a (T, 2) array is one row).
+    lengths: the rows' own sample counts (a scalar or one per row, in [1, T]); the mean is then
+    over each row's first lengths[b] steps.  Accumulated in float64; returns a float64 (n_seqs,)
+    tensor (a pure host function)."""
+    sc = torch.as_tensor(np.asarray(scores) if not torch.is_tensor(scores) else scores)
+    sc = sc.detach().cpu()
+    if sc.dim() == 2:
+        sc = sc.unsqueeze(0)
+    if sc.dim() != 3 or sc.shape[2] != 2 or sc.shape[1] < 1:
+        raise ValueError('bits_per_sample: scores must be (n_seqs, T >= 1, 2), got %s'
+                         % (tuple(sc.shape),))
+    n, T = sc.shape[0], sc.shape[1]
+    lp = sc[..., 0].to(torch.float64)
+    if lengths is None:
+        return -lp.mean(1) / math.log(2.0)
+    ln = torch.as_tensor(lengths).reshape(-1).to(torch.int64)
+    if ln.numel() == 1:
+        ln = ln.expand(n)
+    if ln.numel() != n or int(ln.min()) < 1 or int(ln.max()) > T:
+        raise ValueError('bits_per_sample: lengths must be a scalar or (%d,) values in [1, %d]'
+                         % (n, T))
+    keep = torch.arange(T).unsqueeze(0) < ln.unsqueeze(1)
+    return -(lp * keep).sum(1) / ln.to(torch.float64) / math.log(2.0)
+
+
 def session_chunk_check(level, max_frames, frames, have_spk, temperature=None, top_k=None,
                         top_p=None, prefix=None):
     """What GenSession.chunk refuses before anything runs (a pure host function; the library
@@ -1290,17 +1318,27 @@ class GenSession:
     spk.  What a chunk generates is what the Generator.__call__ with state=<the session's
     state>, stream_ids=<the rows' ids> and the same inputs generates, bit for bit.
 
+    scores=True opens the session for score pairs (level 3: every control and a forced prefix
+    allowed; the arena grows by 8 bytes per row-step): chunk_scored(...) is then chunk(...)
+    with the chunk's host float32 (n_seqs, T, 2) scores (Generator.__call__'s) appended.
+
     steps   (n_seqs,) int64 host tensor: the steps each row has completed.
     last_sequences   the last chunk's sample indices, (n_seqs, frames * lookback) on the device.
     Use after close() raises RuntimeError; a session is a context manager."""
 
     def __init__(self, generator, n_seqs, max_frames, dtype=None, level=0, seed=0,
                  persistent=True, use_graph=True, return_logp=False, replay_noise=False,
-                 row_offset=0):
+                 row_offset=0, scores=False):
         import custom_ops
         model = generator.model
         self.model = model
         self.n_seqs, self.max_frames, self.level = int(n_seqs), int(max_frames), int(level)
+        if self.level not in (0, 1, 2):
+            raise ValueError('GenSession: level must be 0, 1 or 2 (scores=True opens the scored '
+                             'level)')
+        self.scores = bool(scores)
+        if self.scores:
+            self.level = 3               # (the scored builds carry every control)
         self.return_logp, self.replay_noise = bool(return_logp), bool(replay_noise)
         self._dev = next(model.parameters()).device
         H.need_cuda(torch.empty(0, device=self._dev))
@@ -1309,7 +1347,8 @@ class GenSession:
         flags = ((H.GEN_SESSION_GRAPH if use_graph else 0) |
                  (0 if persistent else H.GEN_SESSION_PER_SAMPLE) |
                  (H.GEN_SESSION_LOGP if return_logp else 0) |
-                 (H.GEN_SESSION_NOISE if replay_noise else 0))
+                 (H.GEN_SESSION_NOISE if replay_noise else 0) |
+                 (H.GEN_SESSION_SCORE if self.scores else 0))
         with torch.no_grad():
             self._handle, self._arena = custom_ops.gen_session_open(
                 self.weights, self.meta, self.n_seqs, self.max_frames, self.level, seed,
@@ -1333,7 +1372,23 @@ class GenSession:
         previous chunk (at first: required, 1, off, 1, row_offset + b); prefix / prefix_len
         force this chunk only.  noise: this chunk's (T, n_seqs, Q) Exp(1) draws, given exactly
         when the session was opened with replay_noise."""
+        return self._chunk(False, cond, spk, temperature, top_k, top_p, prefix, prefix_len,
+                           stream_ids, noise)
+
+    def chunk_scored(self, cond, spk=None, temperature=None, top_k=None, top_p=None, prefix=None,
+                     prefix_len=None, stream_ids=None, noise=None):
+        """chunk(...) with the chunk's host float32 (n_seqs, T, 2) score pairs appended (last).
+        Only on a session opened with scores=True: ValueError otherwise, before anything runs
+        (the library makes the same check before it queues anything)."""
+        return self._chunk(True, cond, spk, temperature, top_k, top_p, prefix, prefix_len,
+                           stream_ids, noise)
+
+    def _chunk(self, return_scores, cond, spk, temperature, top_k, top_p, prefix, prefix_len,
+               stream_ids, noise):
         handle = self._live()
+        if return_scores and not self.scores:
+            raise ValueError('GenSession.chunk_scored: scores need a session opened with '
+                             'scores=True')
         model, n_seqs, dev = self.model, self.n_seqs, self._dev
         cond = torch.as_tensor(np.asarray(cond) if not torch.is_tensor(cond) else cond)
         if cond.dim() == 2:
@@ -1378,16 +1433,21 @@ class GenSession:
                 raise ValueError('GenSession.chunk: noise must be (T, n_seqs, Q)')
         on = (lambda t: None if t is None else t.to(dev))
         with torch.no_grad():
-            seq, logp = torch.ops.srnn.gen_session_chunk(
-                handle, L, cond.to(dev, torch.float32).contiguous(), row_bias, on(tau), on(k),
-                on(p), on(prefix), on(prefix_len), ids, noise, self.return_logp)
+            args = (handle, L, cond.to(dev, torch.float32).contiguous(), row_bias, on(tau), on(k),
+                    on(p), on(prefix), on(prefix_len), ids, noise, self.return_logp)
+            if return_scores:
+                seq, logp, score = torch.ops.srnn.gen_session_chunk_scored(*args)
+            else:
+                seq, logp = torch.ops.srnn.gen_session_chunk(*args)
         self.steps = steps
         self._have_spk = True
         self.last_sequences = seq
-        out = model.dequantize(seq, Q).cpu()
+        res = (model.dequantize(seq, Q).cpu(),)
         if self.return_logp:
-            return out, logp.permute(1, 0, 2).contiguous()
-        return out
+            res += (logp.permute(1, 0, 2).contiguous(),)
+        if return_scores:
+            res += (score.permute(1, 0, 2).contiguous().cpu(),)
+        return res if len(res) > 1 else res[0]
 
     def state(self):
         """The rows' GenState after the chunks so far (a copy: the session keeps its own)."""
@@ -1496,6 +1556,15 @@ class Generator(Runner):
     fresh_state() returns records of rows that have done no step (a call from them is the call
     from state=None), GenState.cat / replace join states, and serve() runs requests of differing
     lengths through a fixed number of rows (serve_plan states the policy).
+
+    Scores (not in the reference).  return_scores=True appends a host float32 (n_seqs, T, 2)
+    tensor: [..., 0] the log-prob of each step's sample -- the one drawn, or the given one at a
+    forced step; the dense logp gathered there, bit for bit -- and [..., 1] the entropy of the
+    model's softmax at that step, in nats.  Both describe the model's own distribution whatever
+    the controls did to the draw.  8 bytes per row-step where return_logp takes 1 KiB; the index
+    stream is the unscored call's.  score() scores given audio (every step forced),
+    bits_per_sample() reduces scores to bits per sample; stream, serve and session pass scores
+    through.
     """
 
     def __init__(self, model, cuda=False):
@@ -1508,7 +1577,8 @@ class Generator(Runner):
     def __call__(self, n_seqs, seq_len, cond, spk, sampler='torch', seed=0, noise=None,
                  return_logp=False, use_graph=True, dtype=None, persistent=True, row_offset=0,
                  temperature=1.0, top_k=0, top_p=1.0, state=None, return_state=False,
-                 prefix=None, prefix_len=None, stream_ids=None, controls_level=0):
+                 prefix=None, prefix_len=None, stream_ids=None, controls_level=0,
+                 return_scores=False):
         """row_offset: these n_seqs rows are rows [row_offset, row_offset + n_seqs) of a larger
         batch (rank-sharded generation, see shard_generate): the Philox noise (sampler='philox')
         is that of the global rows, so shards reproduce the single-process stream.
@@ -1520,7 +1590,9 @@ class Generator(Runner):
         the call launches exactly what it launches without them.
         stream_ids: the rows' Philox rows and, with `state`, their own step origins (class
         docstring); None: nothing changes.  controls_level: 1 / 2 passes the control arrays of
-        that level even where every row is at its defaults (serve: one build for all calls)."""
+        that level even where every row is at its defaults (serve: one build for all calls).
+        return_scores: appends the (n_seqs, T, 2) scores (class docstring) after logp and before
+        the state; at False the call launches exactly what it launches without it."""
         model = self.model
         self.reset_hidden_states()
         dev = next(model.parameters()).device
@@ -1558,14 +1630,15 @@ class Generator(Runner):
             ids = None                   # (replayed noise: indexed by the call's own rows)
         streaming = (state is not None or return_state or prefix is not None or
                      prefix_len is not None or ids is not None)
-        if streaming:
+        score = None
+        if streaming or return_scores:
             state_blob, step0 = self._stream_state(state, n_seqs, dev, philox and ids is None)
             prefix, prefix_len = forced_prefix(model, n_seqs, T, prefix, prefix_len)
         with torch.no_grad():
             args = (weights, meta, cond, row_bias, noise, int(seed) & ((1 << 63) - 1),
                     int(row_offset), (1 if use_graph else 0) | (0 if persistent else 2),
                     bool(return_logp))
-            if streaming:
+            if streaming or return_scores:
                 # srnn::generate_stream: the same loop from a carried state and / or along a
                 # forced prefix (srnn_generate5); controls at their defaults stay None
                 sargs = args + (
@@ -1574,7 +1647,13 @@ class Generator(Runner):
                     nucleus.to(dev) if nucleus is not None else None, state_blob, step0,
                     prefix.to(dev) if prefix is not None else None,
                     prefix_len.to(dev) if prefix_len is not None else None, bool(return_state))
-                if ids is None:
+                if return_scores:
+                    # srnn::generate_scored: the scored builds, every other input as it is
+                    # (srnn_generate7)
+                    seq, logp, blob, score = torch.ops.srnn.generate_scored(
+                        *sargs, ids.to(dev) if ids is not None else None,
+                        state.steps.to(dev) if state is not None and ids is not None else None)
+                elif ids is None:
                     seq, logp, blob = torch.ops.srnn.generate_stream(*sargs)
                 else:
                     # srnn::generate_rows: with the rows' own Philox origins (srnn_generate6)
@@ -1593,10 +1672,47 @@ class Generator(Runner):
         res = (out,)
         if return_logp:
             res += (logp.permute(1, 0, 2).contiguous(),)
+        if return_scores:
+            res += (score.permute(1, 0, 2).contiguous().cpu(),)
         if return_state:
             before = state.steps if state is not None else torch.zeros(n_seqs, dtype=torch.int64)
             res += (GenState(blob, gen_state_layout(meta), before + T),)
         return res if len(res) > 1 else out
+
+    def score(self, samples, cond, spk, dtype=None, chunk_frames=0):
+        """Scores given audio under the generation path: `samples` ((n_seqs, T) indices, or a
+        float waveform quantised with the model's quantiser, as prefix= accepts; T = num_cond *
+        lookback exactly) is forced at every step, and the result is the host float32
+        (n_seqs, T, 2) scores of __call__(prefix=samples, return_scores=True): the log-prob of
+        each given sample and the model's entropy there (bits_per_sample reduces them).  With
+        chunk_frames > 0 the audio is scored chunk_frames conditioning frames at a time, each
+        call continuing from the last one's state -- the same scores bit for bit, in memory
+        bounded by the chunk."""
+        x = torch.as_tensor(np.asarray(samples) if not torch.is_tensor(samples) else samples)
+        if x.dim() == 1:
+            x = x.unsqueeze(0)
+        cond = torch.as_tensor(np.asarray(cond) if not torch.is_tensor(cond) else cond)
+        fdim = cond.dim() - 2
+        num_cond, L = cond.shape[fdim], self.model.lookback
+        if x.dim() != 2 or x.shape[1] != num_cond * L:
+            raise ValueError('Generator.score: samples of shape %s, expected (n_seqs, %d) = '
+                             'num_cond * lookback samples' % (tuple(x.shape), num_cond * L))
+        n_seqs = x.shape[0]
+        chunk_frames = int(chunk_frames)
+        if chunk_frames < 0:
+            raise ValueError('Generator.score: chunk_frames must be >= 0')
+        # (every step is forced: no noise is needed)
+        kw = dict(sampler='philox', dtype=dtype, return_scores=True)
+        if chunk_frames == 0 or chunk_frames >= num_cond:
+            return self(n_seqs, 0, cond, spk, prefix=x, **kw)[-1]
+        parts, state = [], None
+        for f0 in range(0, num_cond, chunk_frames):
+            f1 = min(num_cond, f0 + chunk_frames)
+            _, sc, state = self(n_seqs, 0, cond.narrow(fdim, f0, f1 - f0), spk, state=state,
+                                return_state=True, prefix=x[:, f0 * L:f1 * L], **kw)
+            parts.append(sc)
+        self.last_state = state
+        return torch.cat(parts, 1)
 
     @staticmethod
     def _stream_state(state, n_seqs, dev, philox):
@@ -1632,7 +1748,8 @@ class Generator(Runner):
         return GenState(blob, gen_state_layout(meta), torch.zeros(n_seqs, dtype=torch.int64))
 
     def session(self, n_seqs, max_frames, dtype=None, level=0, seed=0, persistent=True,
-                use_graph=True, return_logp=False, replay_noise=False, row_offset=0):
+                use_graph=True, return_logp=False, replay_noise=False, row_offset=0,
+                scores=False):
         """A GenSession of n_seqs rows for chunks of at most max_frames conditioning frames:
         the generation weights (SNAPSHOT here: later parameter updates are not seen), the
         workspace, the rows' records -- fresh ones -- and the captured blocks are kept between
@@ -1640,12 +1757,13 @@ class Generator(Runner):
         top_k / prefix, 2 with top_p); seed: the Philox seed of every chunk; replay_noise: every
         chunk brings its noise (sampler='torch' streams), else the device draws it;
         row_offset: the Philox row of row b is row_offset + b until a chunk gives stream_ids.
-        dtype, persistent, use_graph, return_logp: as in __call__."""
+        dtype, persistent, use_graph, return_logp: as in __call__.  scores: its chunks may
+        return score pairs (GenSession.chunk_scored)."""
         return GenSession(self, n_seqs, max_frames, dtype, level, seed, persistent, use_graph,
-                          return_logp, replay_noise, row_offset)
+                          return_logp, replay_noise, row_offset, scores)
 
     def serve(self, requests, slots, chunk_frames, seed=0, dtype=None, persistent=True,
-              use_graph=True, session=False):
+              use_graph=True, session=False, scores=False):
         """Continuous batching: runs `requests` -- dicts with cond (F_u, C) and spk, optionally
         stream_id (default: the request's position), temperature, top_k, top_p -- through `slots`
         rows by serve_plan's calls (sampler='philox' only), and yields (position, host float32
@@ -1655,7 +1773,9 @@ class Generator(Runner):
         control, every call passes per-row control arrays (defaults for the other rows).
         self.last_serve: {'calls', 'frames' (per call), 'row_frames'} of the run.
         session=True runs the same plan as the chunks of one GenSession, new requests replacing
-        their rows' records by fresh ones: the same yields, without the calls' set-up."""
+        their rows' records by fresh ones: the same yields, without the calls' set-up.
+        scores=True yields (position, samples, host float32 (F_u * lookback, 2) scores): row 0 of
+        that one-shot call's return_scores result."""
         requests = list(requests)
         slots = int(slots)
         conds = []
@@ -1677,10 +1797,10 @@ class Generator(Runner):
         fresh = self.fresh_state(slots, dtype)
         if session:
             yield from self._serve_session(requests, conds, plan, ids, level, fresh, seed, dtype,
-                                           persistent, use_graph)
+                                           persistent, use_graph, scores)
             return
         state = fresh
-        parts = {}
+        parts, sparts = {}, {}
         for n, rows in plan:
             cond = torch.zeros(slots, n, C)
             spk = torch.zeros(slots, dtype=torch.long)
@@ -1698,10 +1818,11 @@ class Generator(Runner):
             new = [s for s, row in enumerate(rows) if row[3]]
             if new:
                 state = state.replace(new, fresh.rows(new))
-            out, state = self(slots, 0, cond, spk, sampler='philox', seed=seed, dtype=dtype,
-                              persistent=persistent, use_graph=use_graph, state=state,
-                              return_state=True, stream_ids=sid, temperature=tau, top_k=k,
-                              top_p=p, controls_level=level)
+            res = self(slots, 0, cond, spk, sampler='philox', seed=seed, dtype=dtype,
+                       persistent=persistent, use_graph=use_graph, state=state,
+                       return_state=True, stream_ids=sid, temperature=tau, top_k=k,
+                       top_p=p, controls_level=level, return_scores=bool(scores))
+            out, state = res[0], res[-1]
             self.last_serve['calls'] += 1
             self.last_serve['frames'].append(n)
             self.last_serve['row_frames'] += slots * n
@@ -1709,17 +1830,23 @@ class Generator(Runner):
                 if u is None:
                     continue
                 parts.setdefault(u, []).append(out[s, :(f1 - f0) * L])
+                if scores:
+                    sparts.setdefault(u, []).append(res[1][s, :(f1 - f0) * L])
                 if f1 == conds[u].shape[0]:
-                    yield u, torch.cat(parts.pop(u))
+                    if scores:
+                        yield u, torch.cat(parts.pop(u)), torch.cat(sparts.pop(u))
+                    else:
+                        yield u, torch.cat(parts.pop(u))
 
     def _serve_session(self, requests, conds, plan, ids, level, fresh, seed, dtype, persistent,
-                       use_graph):
+                       use_graph, scores=False):
         """serve's calls as the chunks of one session (same plan, same per-row inputs)."""
         slots, C, L = fresh.n_seqs, conds[0].shape[1], self.model.lookback
-        parts = {}
+        parts, sparts = {}, {}
         last_spk = None
+        opts = dict(scores=True) if scores else {}
         with self.session(slots, max(n for n, _ in plan), dtype=dtype, level=level, seed=seed,
-                          persistent=persistent, use_graph=use_graph) as sess:
+                          persistent=persistent, use_graph=use_graph, **opts) as sess:
             for n, rows in plan:
                 cond = torch.zeros(slots, n, C)
                 spk = torch.zeros(slots, dtype=torch.long)
@@ -1744,7 +1871,10 @@ class Generator(Runner):
                 if level >= 2:
                     ctl.update(top_p=p)
                 same_spk = last_spk is not None and torch.equal(spk, last_spk)
-                out = sess.chunk(cond, spk=None if same_spk else spk, stream_ids=sid, **ctl)
+                run = sess.chunk_scored if scores else sess.chunk
+                out = run(cond, spk=None if same_spk else spk, stream_ids=sid, **ctl)
+                if scores:
+                    out, sc = out
                 last_spk = spk
                 self.last_serve['calls'] += 1
                 self.last_serve['frames'].append(n)
@@ -1753,14 +1883,20 @@ class Generator(Runner):
                     if u is None:
                         continue
                     parts.setdefault(u, []).append(out[s, :(f1 - f0) * L])
+                    if scores:
+                        sparts.setdefault(u, []).append(sc[s, :(f1 - f0) * L])
                     if f1 == conds[u].shape[0]:
-                        yield u, torch.cat(parts.pop(u))
+                        if scores:
+                            yield u, torch.cat(parts.pop(u)), torch.cat(sparts.pop(u))
+                        else:
+                            yield u, torch.cat(parts.pop(u))
 
     def _stream_session(self, n_seqs, cond, spk, chunk_frames, state, kw):
         """stream's calls as the chunks of one session."""
         kw = dict(kw)
         sampler, noise = kw.pop('sampler', 'torch'), kw.pop('noise', None)
         logp = bool(kw.pop('return_logp', False))
+        scores = bool(kw.pop('return_scores', False))
         tau, k, p = kw.pop('temperature', 1.0), kw.pop('top_k', 0), kw.pop('top_p', 1.0)
         ids = kw.pop('stream_ids', None)
         level = max(int(kw.pop('controls_level', 0)),
@@ -1782,7 +1918,7 @@ class Generator(Runner):
                                  'under sampler=\'philox\' (replayed noise can)'
                                  % sorted(set(state.steps.tolist())))
         with self.session(n_seqs, min(chunk_frames, num_cond), level=level, return_logp=logp,
-                          replay_noise=replay, **kw) as sess:
+                          replay_noise=replay, scores=scores, **kw) as sess:
             if state is not None:
                 sess.replace(list(range(n_seqs)), state)
             ctl = dict(spk=spk, stream_ids=None if replay else ids)
@@ -1796,7 +1932,8 @@ class Generator(Runner):
                 if replay:
                     q = (noise[f0 * L:f1 * L] if noise is not None else
                          torch.empty((f1 - f0) * L, n_seqs, Q).exponential_(1))
-                res = sess.chunk(cond.narrow(fdim, f0, f1 - f0), noise=q, **ctl)
+                res = (sess.chunk_scored if scores else sess.chunk)(
+                    cond.narrow(fdim, f0, f1 - f0), noise=q, **ctl)
                 ctl = {}
                 if f1 == num_cond:
                     self.last_state = sess.state()
@@ -1805,7 +1942,9 @@ class Generator(Runner):
     def stream(self, n_seqs, cond, spk, chunk_frames, state=None, session=False, **kw):
         """Generates chunk_frames conditioning frames per call of __call__, each continuing from
         the state the previous one ended in, and yields every chunk's host float32
-        (n_seqs, frames * lookback) block as it completes (with return_logp: (block, logp)).
+        (n_seqs, frames * lookback) block as it completes (with return_logp: (block, logp); with
+        return_scores the chunk's (n_seqs, frames * lookback, 2) scores come last: (block,
+        scores) or (block, logp, scores)).
         The concatenation equals the single __call__ over all of cond, for either sampler:
         sampler='torch' draws each chunk's noise when the chunk starts -- the CPU generator's
         exponential_ stream does not depend on how it is cut -- so host memory is bounded by
@@ -1827,7 +1966,6 @@ class Generator(Runner):
         num_cond = cond.shape[fdim]
         L = self.model.lookback
         noise = kw.pop('noise', None)
-        logp = kw.get('return_logp', False)
         for f0 in range(0, num_cond, chunk_frames):
             f1 = min(num_cond, f0 + chunk_frames)
             res = self(n_seqs, 0, cond.narrow(fdim, f0, f1 - f0), spk, state=state,
@@ -1835,7 +1973,7 @@ class Generator(Runner):
                        noise=None if noise is None else noise[f0 * L:f1 * L], **kw)
             state = res[-1]
             self.last_state = state
-            yield (res[0], res[1]) if logp else res[0]
+            yield res[:-1] if len(res) > 2 else res[0]
 
     def prime(self, prefix, cond, spk, **kw):
         """The GenState after the given audio: a call forced along all of `prefix` ((n_seqs, T)

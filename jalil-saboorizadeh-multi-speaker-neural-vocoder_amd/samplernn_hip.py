@@ -113,17 +113,21 @@ _SIGS = {
                        _P],
     'srnn_generate6': [_P, _I, _I, _P, _P, _P, _U64, _I, _P, _P, _P, _SZ, _I, _P, _P, _P, _P,
                        _P, _P],
+    'srnn_generate7': [_P, _I, _I, _P, _P, _P, _U64, _I, _P, _P, _P, _SZ, _I, _P, _P, _P, _P,
+                       _P, _P, _P],
     'srnn_gen_state_fresh': [_P, _I, _P, _SZ, _P, _SZ, _P],
     'srnn_gen_state_bytes': [_P, _I],          # (returns size_t, not a status: see _Lib)
     'srnn_gen_session_bytes': [_P, _I, _I, _I, _I, ctypes.POINTER(_SZ)],
     'srnn_gen_session_open': [_P, _I, _I, _I, _U64, _I, _I, _P, _SZ, _P, ctypes.POINTER(_P)],
     'srnn_gen_session_chunk': [_P, _P, _P],
+    'srnn_gen_session_chunk2': [_P, _P, _P, _P],
     'srnn_gen_session_sync': [_P],
     'srnn_gen_session_state_get': [_P, _P, _SZ],
     'srnn_gen_session_state_set_rows': [_P, _P, _I, _P, _SZ, _P],
     'srnn_gen_session_stats': [_P, _P],
     'srnn_gen_session_close': [_P],
     'srnn_sample_rows': [_P, _L, _I, _P, _U64, _I, _I, _P, _P, _P, _P, _P, _P],
+    'srnn_sample_rows2': [_P, _L, _I, _P, _U64, _I, _I, _P, _P, _P, _P, _P, _P, _P],
     'srnn_persistent_flag_to_f32': [_P, _P],
     'srnn_persistent_flag_or_f32': [_P, _P],
     'srnn_persistent_flag_snapshot': [_P, _P],
@@ -168,6 +172,7 @@ class SrnnGenRows(ctypes.Structure):
 
 
 GEN_SESSION_GRAPH, GEN_SESSION_PER_SAMPLE, GEN_SESSION_LOGP, GEN_SESSION_NOISE = 1, 2, 4, 8
+GEN_SESSION_SCORE = 16
 
 
 class SrnnGenChunk(ctypes.Structure):
@@ -504,13 +509,16 @@ def gru_seq_supported(dtype, B, D):
     return bool(_gru_query('srnn_gru_seq_supported', _I, dtype, B, D))
 
 
-def gen_persistent_rows(dtype, n_seqs, dim, fs0, q_levels=256, ctrl=False):
+def gen_persistent_rows(dtype, n_seqs, dim, fs0, q_levels=256, ctrl=False, scores=False):
     """Rows per group of the persistent generation loop for this shape (0: per-sample
     kernels); ctrl: of a call with sampling controls (the controlled build's plan) -- True or 1
-    with temperature / top_k, 2 with top_p as well."""
+    with temperature / top_k, 2 with top_p as well; scores: of a scored call (the scored
+    build's plan, level 3, whatever its controls)."""
     level = int(ctrl)
     if level not in (0, 1, 2):
         raise ValueError('gen_persistent_rows: ctrl must be False, True, 1 or 2')
+    if scores:
+        level = 3
     fn = lib().dll.srnn_gen_persistent_rows_level
     fn.argtypes = [_I, _I, _I, _I, _I, _I]
     fn.restype = _I
@@ -518,7 +526,7 @@ def gen_persistent_rows(dtype, n_seqs, dim, fs0, q_levels=256, ctrl=False):
 
 
 def sample_rows(logits, noise=None, seed=0, row0=0, step=0, temperature=None, top_k=None,
-                top_p=None, return_logp=False):
+                top_p=None, return_logp=False, return_scores=False):
     """One draw per row of `logits` (rows, 256) by the engine's sampler (the registered op
     srnn::sample_rows -> srnn_sample_rows: the device functions of the generation loops, at
     the control level the arrays imply).  noise: (rows, 256) Exp(1) draws, or None for the
@@ -526,8 +534,14 @@ def sample_rows(logits, noise=None, seed=0, row0=0, step=0, temperature=None, to
     / top_k / top_p: None or one value per row (float32 / int32 / float32 tensors; see
     model.sampling_controls and model.nucleus_control for the domains -- the kernel does not
     validate).  Returns the (rows,) int64 indices, with return_logp also the (rows, 256)
-    log_softmax(logits)."""
+    log_softmax(logits), with return_scores (srnn::sample_rows_scored) then the (rows, 2) float32
+    pairs {log-prob of the index drawn, entropy of softmax(logits) in nats}."""
     import custom_ops  # noqa: F401  (registers the op)
+    if return_scores:
+        idx, logp, score = torch.ops.srnn.sample_rows_scored(
+            logits, noise, int(seed) & ((1 << 63) - 1), int(row0), int(step), temperature, top_k,
+            top_p, bool(return_logp))
+        return (idx, logp, score) if return_logp else (idx, score)
     idx, logp = torch.ops.srnn.sample_rows(logits, noise, int(seed) & ((1 << 63) - 1), int(row0),
                                            int(step), temperature, top_k, top_p,
                                            bool(return_logp))
